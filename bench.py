@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- RoIRotate forward throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one forward pass of the hot path (prologue relayout + gather kernel)
 over one batch of synthetic input already resident in HBM:  BASELINE.json
@@ -15,6 +15,10 @@ environment) or, when those are absent, spawns its N ranks itself.
 Prints ONE JSON line on rank 0.
   value            ROIs/s of the whole job: K steps after W warm-up steps, wall clock between
                    barrier + synchronize on both sides, max over ranks.
+  ms_per_step      milliseconds of one timed step (the same wall clock / K).
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if given and prints the
+headline fields above (with `config`).  Everything below is measured only with --full:
   roofline         the dominant kernel (rroi_fwd_split_kernel): algorithmic bytes of one launch /
                    its average duration INSIDE the step (`kernel_ms.avg` = the whole call minus the
                    prologue, each between two HIP events on the launch stream over fixed loops that
@@ -35,6 +39,12 @@ Prints ONE JSON line on rank 0.
                    step as SURVEY 8(e) asks; `ranks`: what every rank ran on (device UUID, architecture)
                    and its own ms_per_step -- two ranks on one device fail the run (outside the
                    one-device self-test).
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's crops) as .npy files:
+  crops_sample.npy       float32 (64, 256, 8, 64): the crops of a fixed, seeded sample of 64 of the
+                         512 ROIs, in ROI order (the whole output is 256 MiB)
+  crops_sum_per_roi.npy  float64 (512,): the sum of every ROI's crop
+The inputs are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -56,6 +66,7 @@ sys.path.insert(0, os.path.join(ROOT, "fots.pytorch_amd"))
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 KERNEL_WARM, KERNEL_TIMED = 300, 500  # the roofline loop, fixed
+DUMP_ROIS, DUMP_SEED = 64, 2024  # --dump-outputs: the seeded sample of ROIs whose crops are written whole
 TOUCHED_PIXELS_RANK0 = 25278  # distinct map pixels the 512 seeded ROIs of configs[1] read (oracle.touched_pixels)
 
 CFG = dict(R=512, C=256, H=160, W=160, img=640, PH=8, PW=64, scale=0.25)
@@ -73,6 +84,17 @@ def make_inputs(R, C=256, H=160, W=160, img=640, seed=0):
     ang = rng.uniform(-90, 90, R)
     rois = np.stack([np.zeros(R), cx, cy, h, w, ang], 1).astype(np.float32)
     return feats, rois
+
+
+def dump_outputs(out, d):
+    """--dump-outputs: the crops the last timed step wrote into `out` (see the header for the two files)."""
+    os.makedirs(d, exist_ok=True)
+    R = out.shape[0]
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(R, size=min(DUMP_ROIS, R), replace=False))
+    sample = out[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+    sums = out.sum(dim=(1, 2, 3), dtype=torch.float64).cpu().numpy()
+    np.save(os.path.join(d, "crops_sample.npy"), sample.astype(np.float32, copy=False))
+    np.save(os.path.join(d, "crops_sum_per_roi.npy"), sums.astype(np.float64, copy=False))
 
 
 def cpu_baseline(feats, rois):
@@ -124,6 +146,23 @@ def cpu_baseline(feats, rois):
         "ms_per_step": round(best * 1e3, 2),
         "backward": backward,
     }, touched
+
+
+def headline(args, world, R, elapsed):
+    """The fields of the line that a plain run prints (and a --full run begins with)."""
+    c = CFG
+    return {
+        "metric": "RoIRotate forward ROIs/sec", "value": round(R * world * args.steps / elapsed, 1), "unit": "ROIs/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 5), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": ("configs[1]" if world == 1 else "configs[3] (%d ROIs sharded over %d GPUs)" % (R * world, world))
+                               + ": features 1x256x160x160 fp32 NCHW%s, %d rotated ROIs/GPU, "
+                               "pooled 8x64, spatial_scale 0.25, forward" % (" replicated" if world > 1 else "", R),
+                   "rois_per_gpu": R, "rois_total": R * world, "channels": c["C"],
+                   "pooled": [c["PH"], c["PW"]], "path": "prologue(relayout+affine) + tiled gather (gatherer + storer waves)",
+                   "parallelism": "roi-shard x%d, no data-path collective" % world},
+    }
 
 
 def _free_port():
@@ -199,10 +238,16 @@ def main():
     # defaults sized so that the run ends in well under a minute; the driver passes its own K / W
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=300)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, CPU baseline and side legs (by default only the headline is measured)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" in os.environ:          # launched by torch.distributed.run: one rank per GPU
         if int(os.environ["WORLD_SIZE"]) != args.gpus:
@@ -296,11 +341,17 @@ def run(args):
         torch.mul(warm_src, 1.0001, out=warm_dst)
     del warm_src, warm_dst
     launch(ext.STAGE_ALL)
-    gather_ms = event_loop(lambda: launch(ext.STAGE_GATHER), KERNEL_WARM, KERNEL_TIMED)
-    prologue_ms = event_loop(lambda: launch(ext.STAGE_PROLOGUE), 100, 200)
-    # the whole call by the same clock (two HIP events around back-to-back calls): a second, independent
-    # reading of the step next to the wall-clock one below, and the state the timed region starts from
-    step_events_ms = event_loop(lambda: launch(ext.STAGE_ALL), 100, 300)
+    if args.full:
+        gather_ms = event_loop(lambda: launch(ext.STAGE_GATHER), KERNEL_WARM, KERNEL_TIMED)
+        prologue_ms = event_loop(lambda: launch(ext.STAGE_PROLOGUE), 100, 200)
+        # the whole call by the same clock (two HIP events around back-to-back calls): a second, independent
+        # reading of the step next to the wall-clock one below, and the state the timed region starts from
+        step_events_ms = event_loop(lambda: launch(ext.STAGE_ALL), 100, 300)
+    else:
+        # no readings: as many untimed calls as the three loops above launch, so that the timed steps
+        # start from the same settled state
+        for _ in range(KERNEL_WARM + KERNEL_TIMED + 300 + 400):
+            launch(ext.STAGE_ALL)
 
     # The first short burst after a long back-to-back run pays for the runtime's housekeeping of the thousands
     # of completed launches (measured in a probe of the same shape: first 20-step segment 60-62 us per step, every later one
@@ -324,6 +375,32 @@ def run(args):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if one_device else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+
+    # ---- N > 1: what every rank ran on; two ranks on one device fail the run ---------------------
+    ranks_info = None
+    if world > 1:
+        prop = torch.cuda.get_device_properties(dev)
+        mine = {"rank": rank, "local_rank": local, "device": torch.cuda.current_device(),
+                "uuid": str(getattr(prop, "uuid", "")), "arch": getattr(prop, "gcnArchName", ""),
+                "name": prop.name, "ms_per_step": round(elapsed_local / args.steps * 1e3, 5)}
+        ranks_info = [None] * world
+        dist.all_gather_object(ranks_info, mine)
+        uuids = [r["uuid"] for r in ranks_info]
+        if not one_device and len(set(uuids)) != world:
+            raise SystemExit("bench.py: %d ranks but the devices are %s -- two ranks share a GPU" % (world, uuids))
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, R, elapsed)))
+            sys.stdout.flush()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full from here on: nothing below enters `value` ----------------------------------------
 
     # ---- N > 1, on the side: the step followed by the all_gather of the crops -------------------
     with_gather_ms = gather_err = None
@@ -351,8 +428,8 @@ def run(args):
         except Exception as e:  # a backend that cannot gather device tensors (self-test over gloo)
             gather_err = repr(e)[:200]
 
-    # ---- N > 1: the feature gradient's all_reduce (25 MiB) and what every rank ran on -----
-    with_allreduce_ms = allreduce_err = ranks_info = None
+    # ---- N > 1: the feature gradient's all_reduce (25 MiB) --------------------------------
+    with_allreduce_ms = allreduce_err = None
     if world > 1:
         try:
             grad = torch.zeros((1, c["C"], c["H"], c["W"]), dtype=torch.float32, device="cpu" if one_device else dev)
@@ -372,15 +449,6 @@ def run(args):
             del grad
         except Exception as e:
             allreduce_err = repr(e)[:200]
-        prop = torch.cuda.get_device_properties(dev)
-        mine = {"rank": rank, "local_rank": local, "device": torch.cuda.current_device(),
-                "uuid": str(getattr(prop, "uuid", "")), "arch": getattr(prop, "gcnArchName", ""),
-                "name": prop.name, "ms_per_step": round(elapsed_local / args.steps * 1e3, 5)}
-        ranks_info = [None] * world
-        dist.all_gather_object(ranks_info, mine)
-        uuids = [r["uuid"] for r in ranks_info]
-        if not one_device and len(set(uuids)) != world:
-            raise SystemExit("bench.py: %d ranks but the devices are %s -- two ranks share a GPU" % (world, uuids))
 
     # spread of the call (median / p10 / p90 over individually bracketed calls; an event between
     # two launches costs ~1-2 us of its own, so these sit above the back-to-back average) and the two
@@ -578,7 +646,6 @@ def run(args):
         return
 
     ms_per_step = elapsed / args.steps * 1e3
-    value = R * world * args.steps / elapsed
 
     cpu, touched = (None, None)
     if world == 1 and not args.no_cpu_baseline:
@@ -647,17 +714,8 @@ def run(args):
         except Exception:
             traffic = None
 
-    line = {
-        "metric": "RoIRotate forward ROIs/sec", "value": round(value, 1), "unit": "ROIs/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 5), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": ("configs[1]" if world == 1 else "configs[3] (%d ROIs sharded over %d GPUs)" % (R * world, world))
-                               + ": features 1x256x160x160 fp32 NCHW%s, %d rotated ROIs/GPU, "
-                               "pooled 8x64, spatial_scale 0.25, forward" % (" replicated" if world > 1 else "", R),
-                   "rois_per_gpu": R, "rois_total": R * world, "channels": c["C"],
-                   "pooled": [c["PH"], c["PW"]], "path": "prologue(relayout+affine) + tiled gather (gatherer + storer waves)",
-                   "parallelism": "roi-shard x%d, no data-path collective" % world},
+    line = headline(args, world, R, elapsed)
+    line.update({
         "roofline": {"bound": "hbm", "kernel": "rroi_fwd_split_kernel", "achieved": round(achieved, 1),
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                      "whole_call_frac": round(b_alg / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
@@ -734,7 +792,7 @@ def run(args):
             "beyond_cache": big,
             "e2e": e2e,
         },
-    }
+    })
     print(json.dumps(line))
     sys.stdout.flush()
     if dist is not None:

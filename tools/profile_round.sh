@@ -7,11 +7,11 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/round
 rm -rf $OUT; mkdir -p $OUT
-python bench.py > $OUT/bench_line.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err
 RROI_BENCH_TRAFFIC=0 RROI_BENCH_E2E=0 RROI_BENCH_SENSITIVITY=0 RROI_BENCH_TRAIN=0 RROI_BENCH_BIG=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- \
-    python bench.py --no-cpu-baseline > $OUT/stats.log 2>&1
+    python bench.py --full --no-cpu-baseline > $OUT/stats.log 2>&1
 # the driver's flags (K = 20 after W = 5), for the record
-python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_line_driver_flags.json 2>> $OUT/bench.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/bench_line_driver_flags.json 2>> $OUT/bench.err
 cp $OUT/stats/*kernel_stats.csv $OUT/bench_kernel_stats.csv 2>/dev/null || \
     find $OUT/stats -name '*kernel_stats.csv' -exec cp {} $OUT/bench_kernel_stats.csv \;
 for c in FETCH_SIZE WRITE_SIZE; do
