@@ -176,10 +176,12 @@ void direct_grid(int num_rois, int NB, int channels, dim3& grid, int& cslab)
 }
 
 // K2p, the direct path (rroi_fwd_patch_kernel): workgroup = (ROI, patch of up to 64 bins, four channel slabs of `cw` channels).
+struct PatchPlan {
+    int prows = 4, pcols = 16, npx = 0, npatches = 0, cw = 0;
+    dim3 grid;
+};
 // Returns false where the form does not apply (the caller falls back to rounds 1-4's thread-per-bin kernel).
-bool launch_patch_forward(const float* features, const float* rois, float* top_data, float* idx_x, float* idx_y, int num_rois,
-                          int channels, int height, int width, int pooled_height, int pooled_width, float spatial_scale, int trig,
-                          int batch_size, hipStream_t stream)
+bool plan_patch_forward(int num_rois, int channels, int width, int pooled_height, int pooled_width, PatchPlan& p)
 {
     const long NB = (long)pooled_height * pooled_width;
     if (!g_tune.fwd_patch || width < 2 || (long)num_rois * NB >= (1L << 30)) return false;
@@ -208,15 +210,27 @@ bool launch_patch_forward(const float* features, const float* rois, float* top_d
     const dim3 pgrid((unsigned)((long)num_rois * npatches), (unsigned)ceil_div(channels, 4 * cw), 1);
     if (pgrid.y > 65535u) return false;
     // (tools/patch_sweep.py: 2-8 K waves, 8-32 channels per wave, 4 or 8 in flight -- all within 0.3 us)
-    if (idx_x)
-        hipLaunchKernelGGL((rroi_fwd_patch_kernel<4, true>), pgrid, dim3(256), 0, stream, features, rois, top_data, num_rois, channels,
-                           height, width, pooled_height, pooled_width, spatial_scale, trig, batch_size, cw, npx, npatches, prows, pcols,
-                           idx_x, idx_y);
-    else
-        hipLaunchKernelGGL((rroi_fwd_patch_kernel<4, false>), pgrid, dim3(256), 0, stream, features, rois, top_data, num_rois, channels,
-                           height, width, pooled_height, pooled_width, spatial_scale, trig, batch_size, cw, npx, npatches, prows, pcols,
-                           (float*)nullptr, (float*)nullptr);
+    p.prows = prows;
+    p.pcols = pcols;
+    p.npx = npx;
+    p.npatches = npatches;
+    p.cw = cw;
+    p.grid = pgrid;
     return true;
+}
+
+void launch_patch_forward(const PatchPlan& p, const float* features, const float* rois, float* top_data, float* idx_x,
+                          float* idx_y, int num_rois, int channels, int height, int width, int pooled_height, int pooled_width,
+                          float spatial_scale, int trig, int batch_size, hipStream_t stream)
+{
+    if (idx_x)
+        hipLaunchKernelGGL((rroi_fwd_patch_kernel<4, true>), p.grid, dim3(256), 0, stream, features, rois, top_data, num_rois, channels,
+                           height, width, pooled_height, pooled_width, spatial_scale, trig, batch_size, p.cw, p.npx, p.npatches,
+                           p.prows, p.pcols, idx_x, idx_y);
+    else
+        hipLaunchKernelGGL((rroi_fwd_patch_kernel<4, false>), p.grid, dim3(256), 0, stream, features, rois, top_data, num_rois, channels,
+                           height, width, pooled_height, pooled_width, spatial_scale, trig, batch_size, p.cw, p.npx, p.npatches,
+                           p.prows, p.pcols, (float*)nullptr, (float*)nullptr);
 }
 
 FastDiv make_fastdiv(unsigned d)
@@ -493,6 +507,365 @@ ForwardPlan plan_forward_gather(int num_rois, int channels, int NB, int nchunks,
 }
 
 // ------------------------------------------------------------------------------------
+// The dispatch.  One function per direction decides what a call launches; the launches switch on its fields and the
+// plan query (rroi_align_forward_plan / rroi_align_backward_plan) reports them, so the two cannot disagree.  Host
+// only: no launch, no memory touched (the backward's workspace is carved at address 0 for its sizes).
+// ------------------------------------------------------------------------------------
+bool caller_ok(int caller, bool con_idx_allowed)
+{
+    return caller == RROI_CALLER_NATIVE || caller == RROI_CALLER_LAUNCHER ||
+           (con_idx_allowed && caller == RROI_CALLER_LAUNCHER_CON_IDX);
+}
+
+struct FwdDispatch {
+    int status = 0;                  // 1: the call launches this plan; 0: it refuses its arguments
+    int family = RROI_PLAN_NONE;
+    int trig = RROI_TRIG_DOUBLE;
+    bool launcher = false;           // the reference-ABI launcher: ROIs of images >= 1 by the prologue (launcher_rest) ...
+    bool con_idx = false;            // ... and con_idx written
+    bool out_nhwc = false, zero_copy = false;
+    int nchunks = 0, groups = 1;
+    ForwardPlan gather{FwdKernel::kStrided, 0, 0, 0};   // fused / two-launch
+    PatchPlan patch;                 // K2p
+    dim3 dgrid;                      // thread-per-bin kernel; the launcher's con_idx kernel
+    int cslab = 0;
+};
+
+FwdDispatch plan_forward(int feature_layout, int top_layout, int batch_size, int num_rois, int height, int width,
+                         int channels, int pooled_height, int pooled_width, int path, int caller)
+{
+    FwdDispatch P;
+    if (!caller_ok(caller, true)) return P;
+    if (path & ~(0xff | RROI_PATH_TRIG_FP32)) return P;   // unknown flag bits
+    P.trig = (path & RROI_PATH_TRIG_FP32) ? RROI_TRIG_FP32 : RROI_TRIG_DOUBLE;
+    path &= 0xff;
+    P.launcher = caller != RROI_CALLER_NATIVE;
+    P.con_idx = caller == RROI_CALLER_LAUNCHER_CON_IDX;
+    if (P.launcher) {
+        // the launcher's signature: NCHW in and out, no path, no batch count -- the tiled path knows image 0 only
+        if (feature_layout != RROI_LAYOUT_NCHW || top_layout != RROI_LAYOUT_NCHW || path != RROI_PATH_AUTO) return P;
+        if (!shape_ok(1, num_rois, height, width, channels, pooled_height, pooled_width)) return P;
+        P.status = 1;
+        if (num_rois == 0) return P;
+        const int NB = pooled_height * pooled_width;
+        direct_grid(num_rois, NB, channels, P.dgrid, P.cslab);
+        if (!pick_tiled_fwd(1, channels, height, width, num_rois, NB)) {
+            P.family = plan_patch_forward(num_rois, channels, width, pooled_height, pooled_width, P.patch)
+                           ? RROI_PLAN_FWD_DIRECT_K2P : RROI_PLAN_FWD_DIRECT_THREAD;
+            return P;
+        }
+        P.status = 0;
+        batch_size = 1;
+        path = RROI_PATH_TILED;
+    }
+    if (top_layout != RROI_LAYOUT_NCHW && top_layout != RROI_LAYOUT_NHWC) return P;
+    P.out_nhwc = top_layout == RROI_LAYOUT_NHWC;
+    // channels-last crops are written by the tiled kernel only: 16-byte channel quads
+    if (P.out_nhwc && (channels % 4 != 0 || path == RROI_PATH_DIRECT ||
+                       (long)pooled_height * pooled_width * channels * 4 >= (1L << 31)))
+        return P;
+    if (!shape_ok(batch_size, num_rois, height, width, channels, pooled_height, pooled_width)) return P;
+    if (feature_layout != RROI_LAYOUT_NCHW && feature_layout != RROI_LAYOUT_NHWC) return P;
+    if (path != RROI_PATH_AUTO && path != RROI_PATH_DIRECT && path != RROI_PATH_TILED && path != RROI_PATH_FUSED) return P;
+    if (num_rois == 0) {
+        P.status = 1;
+        return P;
+    }
+    const int NB = pooled_height * pooled_width;
+    P.nchunks = ceil_div(channels, kChunk);
+
+    bool tiled;
+    if (P.out_nhwc)
+        tiled = true;
+    else if (path == RROI_PATH_AUTO)
+        tiled = feature_layout == RROI_LAYOUT_NHWC ||
+                pick_tiled_fwd(batch_size, channels, height, width, num_rois, NB);
+    else
+        tiled = path == RROI_PATH_TILED;
+    // the one-launch form for few ROIs (the gather reading the NCHW map itself): NCHW in, NCHW out, not for the launcher
+    const bool fused = !P.launcher && !P.out_nhwc && feature_layout == RROI_LAYOUT_NCHW &&
+                       (path == RROI_PATH_FUSED ||
+                        (path == RROI_PATH_AUTO && !tiled && pick_fused_fwd(batch_size, channels, height, width, num_rois, NB)));
+    if (path == RROI_PATH_FUSED && !fused) return P;
+    if (fused) {
+        P.gather = plan_forward_gather(num_rois, channels, NB, P.nchunks, false, false, 1, 0, /*allow_lines*/ false);
+        if (P.gather.kernel != FwdKernel::kShift && P.gather.kernel != FwdKernel::kStrided) return P;   // the two forms NCHW_SRC has
+        if ((long)num_rois * P.gather.ntiles >= (1L << 31)) return P;
+        P.family = P.gather.kernel == FwdKernel::kShift ? RROI_PLAN_FWD_FUSED_SHIFT : RROI_PLAN_FWD_FUSED_STRIDED;
+        P.status = 1;
+        return P;
+    }
+    if (!tiled) {
+        if (feature_layout != RROI_LAYOUT_NCHW) return P;  // direct path reads NCHW only
+        if (plan_patch_forward(num_rois, channels, width, pooled_height, pooled_width, P.patch)) {
+            P.family = RROI_PLAN_FWD_DIRECT_K2P;
+        } else {
+            P.family = RROI_PLAN_FWD_DIRECT_THREAD;
+            direct_grid(num_rois, NB, channels, P.dgrid, P.cslab);
+        }
+        P.status = 1;
+        return P;
+    }
+    if (feature_layout == RROI_LAYOUT_NHWC && channels % 4 != 0) return P;  // repack to NCHW first
+    P.zero_copy = feature_layout == RROI_LAYOUT_NHWC;
+    P.groups = P.launcher ? 1 : forward_groups(num_rois, P.nchunks);
+    const size_t map_bytes_per_xcd =
+        P.zero_copy ? (size_t)batch_size * height * width * channels * 4 / 8
+                    : carve(nullptr, batch_size, channels, height, width, num_rois, feature_layout).cm_bytes / 8;
+    P.gather = plan_forward_gather(num_rois, channels, NB, P.nchunks, P.out_nhwc, P.launcher, P.groups, map_bytes_per_xcd);
+    if ((long)num_rois * P.gather.ntiles >= (1L << 31)) return P;
+    P.family = RROI_PLAN_FWD_TWO_LAUNCH;
+    P.status = 1;
+    return P;
+}
+
+struct BwdDispatch {
+    int status = 0;                  // 1: the call launches this plan; 0: it refuses its arguments
+    int family = RROI_PLAN_NONE;
+    int trig = RROI_TRIG_DOUBLE;
+    int dest = RROI_PLAN_DST_NONE;
+    bool td_nhwc = false, bd_nhwc = false, accumulate = false;
+    int nchunks = 0;
+    BwdWorkspace ws{};               // carved at address 0: sizes, key layout, bucket shift
+    dim3 grid;                       // the main kernel's
+    int cslab = 0;                   // direct
+    int ntiles = 0;                  // atomic ...
+    bool vec4 = false;               // ... rroi_bwd_tiled_kernel<true> (NB % 4 == 0)
+    int nk = 0;                      // in-kernel
+    long relayout_blocks = 0;        // in-kernel: the relayout of top_diff (0: consumed in place)
+    int tt = 0;                      // top_diff relayout tiles per (roi, chunk)
+    long tiles = 0, half = 0;        // ... in all; lists: the first launch's share
+    int raw_bsum = -1;
+    int pblocks = 0;
+    bool aggregate = false;
+    unsigned sub_shift = 0, gy = 0, tile_run = 0;
+    long literal_blocks = 0;
+};
+
+// accumulate (the reference-ABI launcher, tiled NCHW paths only): bottom_diff += gradient instead of = gradient
+// AUTO / TILED choose among the gathers; LISTS and INKERNEL name one
+static inline bool gather_choice_is_open(int path)
+{
+    return path != RROI_PATH_TILED_LISTS && path != RROI_PATH_TILED_INKERNEL;
+}
+
+BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch_size, int num_rois, int height, int width,
+                          int channels, int pooled_height, int pooled_width, int path, int caller)
+{
+    BwdDispatch P;
+    if (!caller_ok(caller, false)) return P;
+    if (path & ~(0xff | RROI_PATH_TRIG_FP32)) return P;   // unknown flag bits
+    P.trig = (path & RROI_PATH_TRIG_FP32) ? RROI_TRIG_FP32 : RROI_TRIG_DOUBLE;
+    path &= 0xff;
+    if (caller == RROI_CALLER_LAUNCHER) {
+        if (top_diff_layout != RROI_LAYOUT_NCHW || bottom_diff_layout != RROI_LAYOUT_NCHW || path != RROI_PATH_AUTO) return P;
+        if (!shape_ok(batch_size, num_rois, height, width, channels, pooled_height, pooled_width)) return P;
+        P.accumulate = true;
+        P.status = 1;
+        if (num_rois == 0) return P;   // nothing to add
+        if (!pick_tiled_bwd(batch_size, channels, height, width, num_rois, pooled_height * pooled_width)) {
+            P.family = RROI_PLAN_BWD_LITERAL;
+            P.dest = RROI_PLAN_DST_NCHW_ADD;
+            const long nthreads = (long)num_rois * pooled_height * pooled_width * channels;
+            long blocks = (nthreads + 255) / 256;
+            const long cap = (long)num_cus() * 32;
+            if (blocks > cap) blocks = cap;
+            P.literal_blocks = blocks;
+            P.grid = dim3((unsigned)blocks);
+            return P;
+        }
+        P.status = 0;
+        path = RROI_PATH_TILED;
+    }
+    if (top_diff_layout != RROI_LAYOUT_NCHW && top_diff_layout != RROI_LAYOUT_NHWC) return P;
+    if (bottom_diff_layout != RROI_LAYOUT_NCHW && bottom_diff_layout != RROI_LAYOUT_NHWC) return P;
+    const bool td_nhwc = top_diff_layout == RROI_LAYOUT_NHWC, bd_nhwc = bottom_diff_layout == RROI_LAYOUT_NHWC;
+    P.td_nhwc = td_nhwc;
+    P.bd_nhwc = bd_nhwc;
+    // channels-last tensors are read / written in place by the gather formulation only
+    if ((td_nhwc || bd_nhwc) &&
+        (channels % 4 != 0 || path == RROI_PATH_DIRECT || path == RROI_PATH_TILED_ATOMIC))
+        return P;
+    if (!shape_ok(batch_size, num_rois, height, width, channels, pooled_height, pooled_width)) return P;
+    if (path != RROI_PATH_AUTO && path != RROI_PATH_DIRECT && path != RROI_PATH_TILED &&
+        path != RROI_PATH_TILED_ATOMIC && path != RROI_PATH_TILED_LISTS && path != RROI_PATH_TILED_INKERNEL &&
+        path != RROI_PATH_TILED_BUCKETS)
+        return P;
+    if (num_rois == 0) {   // bottom_diff zeroed
+        P.status = 1;
+        return P;
+    }
+    const int NB = pooled_height * pooled_width;
+    const size_t HW = (size_t)height * width;
+    const bool accumulate = P.accumulate;
+    const bool tiled = td_nhwc || bd_nhwc || (path == RROI_PATH_AUTO
+                                       ? pick_tiled_bwd(batch_size, channels, height, width, num_rois, NB)
+                                       : path != RROI_PATH_DIRECT);
+    if (accumulate && (!tiled || bd_nhwc)) return P;
+    const int nchunks = ceil_div(channels, kChunk);
+    P.nchunks = nchunks;
+    if (!tiled) {
+        direct_grid(num_rois, NB, channels, P.grid, P.cslab);
+        P.family = RROI_PLAN_BWD_DIRECT;
+        P.dest = RROI_PLAN_DST_NCHW;
+        P.status = 1;
+        return P;
+    }
+
+    const BwdWorkspace ws = carve_bwd(nullptr, batch_size, channels, height, width, num_rois, NB);
+    P.ws = ws;
+    if ((td_nhwc || bd_nhwc) && (!ws.gather_ok || (size_t)num_rois * NB >= (1ull << 32))) return P;
+    const bool gather = path != RROI_PATH_TILED_ATOMIC && ws.gather_ok;
+    // Two gathers.  K3t builds the pixel lists inside the gather kernel (rroi_backward_tile_kernels.h), K3g
+    // with count / scan / fill launches in HBM.  Measured (tools/crossover.py, MI355X, us per call,
+    // K3t / K3g): C = 64, 176x320 map, 11x96: R = 4 26 / 33, 32 31 / 37, 128 41 / 49, 512 88 / 98;  C = 64,
+    // 8 images of 160x160, 11x100: 45 / 51, 54 / 54, 68 / 72, 133 / 148;  C = 256, 160x160, 8x64: 39 / 39,
+    // 43 / 40, 77 / 62, 201 / 168 -- K3t's serial work per tile is hidden when a lane carries two
+    // channel chunks, not when it carries eight.  K3t addresses its source with 32-bit byte offsets.
+    const size_t src_bytes = td_nhwc ? (size_t)num_rois * NB * channels * 4
+                                     : (size_t)num_rois * NB * nchunks * kLineBytes;
+    const bool inkernel_ok = src_bytes < (1ull << 32);
+    if (path == RROI_PATH_TILED_INKERNEL && !(gather && inkernel_ok)) return P;
+    // ... with four chunks per lane (C <= 128) it still wins where the lists are short: C = 128, 160x160,
+    // 8x64: R = 32 33 / 42, 128 48 / 48, 512 101 / 93;  C = 96, 176x320, 11x96: 38 / 45, 56 / 61, 114 / 122
+    const bool short_lists = (double)num_rois * NB <= 8.0 * (double)batch_size * HW;   // bins per map pixel
+    // every map tile's workgroup scans ALL the ROIs (in batches of 256): O(tiles x R), measured up to R = 512
+    // and 8 images -- beyond that the lists in HBM, whose cost does not grow that way, are the safe choice
+    const bool scan_ok = (double)num_rois * batch_size <= 8192.0;
+    // round 3 (profiles/r03_crossover.txt): up to 256 channels it also wins while there is at most one bin per map
+    // pixel -- C = 256, 160 x 160, 8 x 64: R = 4 45.9 / 52.8, 16 49.5 / 52.5, 32 49.7 / 53.7, 64 56.9 / 57.4, 128 78.3 / 65.5
+    const bool very_short = (double)num_rois * NB <= 1.0 * (double)batch_size * HW;
+    const bool prefer_inkernel = scan_ok && (nchunks <= 2 || (nchunks <= 4 && short_lists) || (nchunks <= 8 && very_short));
+    if (path == RROI_PATH_TILED_BUCKETS && !(gather && ws.bucket_ok)) return P;
+    // Round 3: the lists in HBM built in ONE pass over the bins (fixed buckets of 2^kshift entries per pixel plus
+    // overflow chains, rroi_backward_kernels.h) instead of count / scan / fill.  Measured (tools/crossover.py,
+    // tools/bucket_ab.py, profiles/r03_crossover_buckets.txt; us per call, buckets / exact lists / K3t): cfg3 129 /
+    // 144 / 179;  C = 256 R = 16 37 / 53 / 48;  C = 64 176x320 R = 128 40 / 48 / 43;  8 images of 160x160 R = 64
+    // 49 / 61 / 61 -- they win wherever the bucket holds at least the average list (128 entries per pixel in buckets
+    // of 128: 74 / 89 / 164) and lose where most of a list lives in the chains (512 per pixel in buckets of 128:
+    // 200 / 128 / 318): the bucket grows with the density as far as carve_bwd's cap lets it, bucket_pref says if
+    // that was far enough.
+    const bool buckets = gather && ws.bucket_ok && gather_choice_is_open(path) &&
+                         (path == RROI_PATH_TILED_BUCKETS || (ws.bucket_pref && g_tune.bwd_buckets));
+    const bool lists = buckets || path == RROI_PATH_TILED_LISTS || !inkernel_ok ||
+                       (path != RROI_PATH_TILED_INKERNEL && !prefer_inkernel);
+    P.tt = ceil_div(NB, kRelayoutPx);
+    if (gather && !lists) {
+        // K3t: relayout of top_diff (one launch, masked bins skipped), then the tile gather
+        P.family = RROI_PLAN_BWD_INKERNEL;
+        if (!td_nhwc) {
+            P.tiles = (long)P.tt * nchunks * num_rois;
+            if (P.tiles >= (1L << 31)) return P;
+            // one block per pixel range (all its chunks), at most 8 resident blocks per CU
+            long blocks = P.tiles / nchunks;
+            const long cap = (long)num_cus() * 8;
+            if (blocks > cap) blocks = cap;
+            P.relayout_blocks = blocks;
+        }
+        P.nk = nchunks > 4 ? 8 : nchunks > 2 ? 4 : nchunks > 1 ? 2 : 1;
+        const unsigned ntiles = ws.keys.keys / 32u;
+        const unsigned per_xcd = (ntiles + 7u) / 8u;
+        P.grid = dim3(per_xcd * 8u);
+        P.dest = bd_nhwc ? RROI_PLAN_DST_NHWC : RROI_PLAN_DST_CHUNK_MAJOR;
+    } else if (gather) {
+        // (1) pixel -> (bin, weight) lists: count, scan, fill -- or buckets in one pass
+        P.family = buckets ? RROI_PLAN_BWD_BUCKETS : RROI_PLAN_BWD_LISTS;
+        // few scan blocks: every consumer block prefix-sums their totals itself (no second scan launch)
+        P.raw_bsum = ws.scan_blocks <= kInlineScanBlocks ? 1 : 0;
+        // one pair block per CU, looping over the bins: the pair passes need outstanding atomics,
+        // not CU slots -- more blocks only take residency from the relayout (207 -> 197 us per call)
+        const PatchMap dnb = make_patch_map(pooled_height, pooled_width);
+        if ((long)num_rois * dnb.lanes_per_roi >= (1L << 32)) return P;
+        int pblocks = ceil_div((long)num_rois * dnb.lanes_per_roi, 256);
+        {
+            // pair blocks per CU.  A pair wave walks a chain of returning atomics (~2.5 us per patch of 64 bins under
+            // load), so its launch time is patches per wave x that; the relayout it shares the launch with takes
+            // bytes / bandwidth.  One block per CU hides the pairs behind the relayout of 256 channels (round 2); with
+            // FEWER channels the same bins bring a quarter of the bytes and the pair pass set the launch (R = 512, C = 64,
+            // 11 x 96: 58 us where the relayout alone takes 30): blocks per CU ~ 256 / C.
+            // (tools/pair_blocks_ab.py, profiles/r05_pair_blocks_ab2.txt: with the wave-aggregated reservations, us per call at 1 / 2
+            // / 4 / 8 blocks per CU -- C = 64, R = 512, 11 x 96: 90.6 / 73.0 / 67.0 / 68.8 (round 4: 84.3); C = 128: 66.5 / 58.9 /
+            // 59.7 / 59.7; configs[2]: 104.4 / 103.3 / 103.6 / 103.5)
+            int per_cu = g_tune.bwd_pair_blocks_per_cu;
+            if (per_cu <= 0) per_cu = std::min(4, std::max(2, 256 / std::max(channels, 1)));
+            // channels-last gradients need no relayout: the pair blocks have the launch to themselves (CL=1 tools/pair_blocks_ab.py,
+            // profiles/r05_pair_blocks_ab_cl.txt: C = 64, R = 512 45.3 / 41.4 us at 4 / 8 per CU, round 4: 64.0; configs[2] 52.8 / 49.0, 51.3)
+            if (g_tune.bwd_pair_blocks_per_cu <= 0 && td_nhwc) per_cu = 8;
+            const long cap = (long)num_cus() * per_cu;
+            if (pblocks > cap) pblocks = (int)cap;
+        }
+        P.pblocks = pblocks;
+        // the bucket slots reserved per WAVE through a table in LDS (pairs_reserve_wave) -- where a wave has several
+        // patches to walk; with one patch per wave the table's set-up is pure latency (R = 32, C = 64: +0.8 us)
+        P.aggregate = g_tune.bwd_pair_aggregate && (long)num_rois * (dnb.lanes_per_roi / 64) > 8L * num_cus();
+        // count || first half of the relayout;  scan;  fill || second half.  The relayout is the
+        // forward's, with R "images" of PH x PW "pixels" and the masked bins skipped:
+        // top_diff (R, C, NB) -> (R, NB, nchunks * 32)
+        P.tiles = td_nhwc ? 0 : (long)P.tt * nchunks * num_rois;  // nothing to relay out
+        if (P.tiles >= (1L << 31)) return P;
+        const long unit = nchunks;  // a block takes all chunks of a pixel range: whole ranges per launch
+        P.half = (P.tiles / 2 + unit - 1) / unit * unit < P.tiles ? (P.tiles / 2 + unit - 1) / unit * unit : P.tiles;
+        // (3) gather: one thread group per key, no grid-stride
+        unsigned sub_shift = 3;  // 8 lanes = one chunk
+        while ((1u << sub_shift) < 8u * (unsigned)nchunks && sub_shift < 6) ++sub_shift;
+        // NCHW bottom_diff written in place (round 4; tools/bwd_nchw_ab.py, profiles/r04_bwd_nchw_ab.txt): a workgroup
+        // needs whole rows (8 pixels) of a key tile, i.e. at most 32 lanes per pixel -- wider pixels (C > 128) deal
+        // their passes of four chunks to blockIdx.y, which walks every list once per pass: that pays while the lists
+        // are short (cfg3, 10 bins per map pixel: 125.6 -> 117.5 us; 20 per pixel: 274 -> 283), so C > 128 keeps the
+        // scratch form beyond 16 bins per pixel.  C <= 128 gains at every density measured: R = 512, C = 64 / 128
+        // 76.0 -> 71.9 / 76.5 -> 71.2, R = 16...32 36.8 -> 29.0 / 24.3 -> 17.9 (the relayout launch was a fifth of
+        // those calls), 84 bins per pixel 159 -> 153.
+        const bool nchw_direct = !bd_nhwc && g_tune.bwd_nchw_direct != 0 &&
+                                 (nchunks <= 4 || (double)num_rois * NB <= (double)g_tune.bwd_nchw_direct * (double)batch_size * HW);
+        unsigned gy = 1;
+        if (nchw_direct && sub_shift == 6) {
+            sub_shift = 5;
+            gy = (unsigned)ceil_div(nchunks, 4);
+        }
+        const unsigned groups_per_block = 256u >> sub_shift;
+        // whole groups of 8 key tiles (the kernel deals the tiles of a group to the 8 XCDs)
+        const long wg_per_tile = 32 / groups_per_block;  // 1, 2, 4 or 8
+        const unsigned tile_run = nchw_direct ? (unsigned)g_tune.bwd_tile_run : 0u;
+        const long gblocks = ceil_div(ceil_div((long)ws.keys.keys, 32L), 8L << tile_run) * (8L << tile_run) * wg_per_tile;
+        P.sub_shift = sub_shift;
+        P.gy = gy;
+        P.tile_run = tile_run;
+        P.grid = dim3((unsigned)gblocks, gy);
+        P.dest = bd_nhwc ? RROI_PLAN_DST_NHWC
+                         : nchw_direct ? (accumulate ? RROI_PLAN_DST_NCHW_ADD : RROI_PLAN_DST_NCHW) : RROI_PLAN_DST_CHUNK_MAJOR;
+    } else {
+        P.family = RROI_PLAN_BWD_ATOMIC;
+        P.ntiles = ceil_div(NB, kTileBins);
+        if ((long)num_rois * P.ntiles >= (1L << 31)) return P;
+        P.grid = dim3(tiled_grid((long)num_rois * P.ntiles, nchunks));
+        P.vec4 = NB % 4 == 0;
+        P.dest = RROI_PLAN_DST_CHUNK_MAJOR;
+    }
+    P.status = 1;
+    return P;
+}
+
+void fill_plan(rroi_align_plan* out, int family, int kernel, int groups, int ntiles, dim3 grid, bool zero_copy, bool con_idx,
+               int nk, int kshift, int raw_bsum, int gy, int dest, bool accumulate, bool vec4)
+{
+    out->family = family;
+    out->kernel = kernel;
+    out->groups = groups;
+    out->ntiles = ntiles;
+    out->grid_x = (int)grid.x;
+    out->grid_y = (int)grid.y;
+    out->zero_copy = zero_copy;
+    out->con_idx = con_idx;
+    out->nk = nk;
+    out->kshift = kshift;
+    out->raw_bsum = raw_bsum;
+    out->gy = gy;
+    out->dest = dest;
+    out->accumulate = accumulate;
+    out->vec4 = vec4;
+}
+
+// ------------------------------------------------------------------------------------
 // Scratch of the reference-ABI launchers.  Their signatures carry no workspace, so the library keeps
 // one buffer per (device, stream), grown on demand and reused: calls on one stream are ordered, so the
 // next call may overwrite what the previous one left.  No allocator round trip per call, and a call
@@ -661,7 +1034,7 @@ ScratchLease launcher_scratch(hipStream_t stream, size_t bytes)
 // ====================================================================================
 extern "C" {
 
-const char* rroi_align_hip_version(void) { return "rroi_align_hip 0.8.0 gfx950"; }
+const char* rroi_align_hip_version(void) { return "rroi_align_hip 0.9.0 gfx950"; }
 
 size_t rroi_align_forward_workspace_bytes(int batch_size, int channels, int height, int width,
                                           int num_rois, int feature_layout)
@@ -695,8 +1068,7 @@ int rroi_align_forward_hip(const float* features, int feature_layout, float spat
 static int forward_impl(const float* features, int feature_layout, int top_layout, float spatial_scale,
                         int batch_size, int num_rois, int height, int width, int channels,
                         int pooled_height, int pooled_width, const float* rois, float* top_data,
-                        void* workspace, size_t workspace_bytes, int path, int stages, void* stream_,
-                        bool launcher_rest = false);
+                        void* workspace, size_t workspace_bytes, int path, int stages, void* stream_);
 
 int rroi_align_forward_stages_hip(const float* features, int feature_layout, float spatial_scale,
                                   int batch_size, int num_rois, int height, int width,
@@ -720,52 +1092,37 @@ int rroi_align_forward_layout_hip(const float* features, int feature_layout, int
                         workspace_bytes, path, RROI_STAGE_ALL, stream_);
 }
 
-// launcher_rest (the reference-ABI launcher; tiled NCHW path): ROIs whose image index is >= batch_size are
-// sampled from the NCHW tensor by extra blocks of the prologue launch and left alone by the gather
-static int forward_impl(const float* features, int feature_layout, int top_layout, float spatial_scale,
-                        int batch_size, int num_rois, int height, int width, int channels,
-                        int pooled_height, int pooled_width, const float* rois, float* top_data,
-                        void* workspace, size_t workspace_bytes, int path, int stages, void* stream_,
-                        bool launcher_rest)
+// Launches the plan `P` (plan_forward on the same arguments).  The launcher's tiled plan (P.launcher): ROIs whose
+// image index is >= batch_size are sampled from the NCHW tensor by extra blocks of the prologue launch and left alone
+// by the gather; its direct kernels get no batch count (-1) and write con_idx where P.con_idx.
+static int launch_forward(const FwdDispatch& P, const float* features, int feature_layout, float spatial_scale,
+                          int batch_size, int num_rois, int height, int width, int channels, int pooled_height,
+                          int pooled_width, const float* rois, float* top_data, float* idx_x, float* idx_y,
+                          void* workspace, size_t workspace_bytes, int stages, hipStream_t stream)
 {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (path & ~(0xff | RROI_PATH_TRIG_FP32)) return 0;   // unknown flag bits
-    const int trig = (path & RROI_PATH_TRIG_FP32) ? RROI_TRIG_FP32 : RROI_TRIG_DOUBLE;
-    path &= 0xff;
-    if ((stages & ~RROI_STAGE_ALL) || stages == 0) return 0;
-    if (top_layout != RROI_LAYOUT_NCHW && top_layout != RROI_LAYOUT_NHWC) return 0;
-    const bool out_nhwc = top_layout == RROI_LAYOUT_NHWC;
-    // channels-last crops are written by the tiled kernel only: 16-byte channel quads
-    if (out_nhwc && (channels % 4 != 0 || path == RROI_PATH_DIRECT ||
-                     (long)pooled_height * pooled_width * channels * 4 >= (1L << 31)))
-        return 0;
-    if (!shape_ok(batch_size, num_rois, height, width, channels, pooled_height, pooled_width))
-        return 0;
-    if (feature_layout != RROI_LAYOUT_NCHW && feature_layout != RROI_LAYOUT_NHWC) return 0;
-    if (path != RROI_PATH_AUTO && path != RROI_PATH_DIRECT && path != RROI_PATH_TILED && path != RROI_PATH_FUSED) return 0;
-    if (num_rois == 0) return 1;
-    if (!features || !rois || !top_data) return 0;
     const int NB = pooled_height * pooled_width;
-
-    bool tiled;
-    if (out_nhwc)
-        tiled = true;
-    else if (path == RROI_PATH_AUTO)
-        tiled = feature_layout == RROI_LAYOUT_NHWC ||
-                pick_tiled_fwd(batch_size, channels, height, width, num_rois, NB);
-    else
-        tiled = path == RROI_PATH_TILED;
-    // the one-launch form for few ROIs (the gather reading the NCHW map itself): NCHW in, NCHW out, not for the launcher
-    const bool fused = !launcher_rest && !out_nhwc && feature_layout == RROI_LAYOUT_NCHW &&
-                       (path == RROI_PATH_FUSED ||
-                        (path == RROI_PATH_AUTO && !tiled && pick_fused_fwd(batch_size, channels, height, width, num_rois, NB)));
-    if (path == RROI_PATH_FUSED && !fused) return 0;
-    if (fused) {
+    const int trig = P.trig;
+    const int nchunks = P.nchunks;
+    const int direct_batch = P.launcher ? -1 : batch_size;   // (the launcher's signature has no batch count)
+    switch (P.family) {
+    case RROI_PLAN_NONE:
+        return 1;
+    case RROI_PLAN_FWD_DIRECT_K2P:
+        if (!(stages & RROI_STAGE_GATHER)) return 1;  // the direct path has no prologue
+        launch_patch_forward(P.patch, features, rois, top_data, P.con_idx ? idx_x : nullptr, P.con_idx ? idx_y : nullptr,
+                             num_rois, channels, height, width, pooled_height, pooled_width, spatial_scale, trig,
+                             direct_batch, stream);
+        return launch_status();
+    case RROI_PLAN_FWD_DIRECT_THREAD:
+        if (!(stages & RROI_STAGE_GATHER)) return 1;
+        hipLaunchKernelGGL(rroi_fwd_direct_kernel, P.dgrid, dim3(256), 0, stream, features, rois, top_data,
+                           P.con_idx ? idx_x : nullptr, P.con_idx ? idx_y : nullptr, num_rois, channels, height, width,
+                           pooled_height, pooled_width, spatial_scale, trig, direct_batch, P.cslab);
+        return launch_status();
+    case RROI_PLAN_FWD_FUSED_STRIDED:
+    case RROI_PLAN_FWD_FUSED_SHIFT: {
         if (!(stages & RROI_STAGE_GATHER)) return 1;  // one launch, run under the gather stage
-        const int nchunks = ceil_div(channels, kChunk);
-        const ForwardPlan plan = plan_forward_gather(num_rois, channels, NB, nchunks, false, false, 1, 0, /*allow_lines*/ false);
-        if (plan.kernel != FwdKernel::kShift && plan.kernel != FwdKernel::kStrided) return 0;   // the two forms NCHW_SRC has
-        if ((long)num_rois * plan.ntiles >= (1L << 31)) return 0;
+        const ForwardPlan& plan = P.gather;
         const unsigned HWu = (unsigned)height * (unsigned)width;
         SliceLayout lay;
         lay.px_bytes = 4u;                       // a "pixel" of a channel plane
@@ -779,36 +1136,25 @@ static int forward_impl(const float* features, int feature_layout, int top_layou
     hipLaunchKernelGGL((rroi_fwd_split_kernel<__VA_ARGS__>), dim3(plan.grid), dim3(2 * kWave), 0, stream, features,          \
                        (const Affine*)nullptr, top_data, num_rois, channels, height, width, pooled_width, NB, batch_size,    \
                        nchunks, plan.ntiles, lay, dt, dp, plan.dbg, XcdGroups{1, nullptr}, rsrc)
-        if (plan.kernel == FwdKernel::kShift) RROI_FUSED(true, 0, 4, 3, false, 1, true);
+        if (P.family == RROI_PLAN_FWD_FUSED_SHIFT) RROI_FUSED(true, 0, 4, 3, false, 1, true);
         else RROI_FUSED(true, 0, 4, 3, false, 0, true);
 #undef RROI_FUSED
         return launch_status();
     }
-    if (!tiled && feature_layout != RROI_LAYOUT_NCHW) return 0;  // direct path reads NCHW only
-
-    if (!tiled) {
-        if (!(stages & RROI_STAGE_GATHER)) return 1;  // the direct path has no prologue
-        if (launch_patch_forward(features, rois, top_data, nullptr, nullptr, num_rois, channels, height, width, pooled_height,
-                                 pooled_width, spatial_scale, trig, batch_size, stream))
-            return launch_status();
-        dim3 grid;
-        int cslab;
-        direct_grid(num_rois, NB, channels, grid, cslab);
-        hipLaunchKernelGGL(rroi_fwd_direct_kernel, grid, dim3(256), 0, stream, features, rois,
-                           top_data, (float*)nullptr, (float*)nullptr, num_rois, channels, height,
-                           width, pooled_height, pooled_width, spatial_scale, trig, batch_size, cslab);
-        return launch_status();
+    case RROI_PLAN_FWD_TWO_LAUNCH:
+        break;
+    default:
+        return 0;
     }
 
-    if (feature_layout == RROI_LAYOUT_NHWC && channels % 4 != 0) return 0;  // repack to NCHW first
     const Workspace ws = carve(workspace, batch_size, channels, height, width, num_rois, feature_layout);
     if (!workspace || workspace_bytes < ws.bytes) return 0;
     const int HW = height * width;
-    const int nchunks = ceil_div(channels, kChunk);
-    const bool zero_copy = feature_layout == RROI_LAYOUT_NHWC;
+    const bool zero_copy = P.zero_copy;
     const float* map = zero_copy ? features : ws.cm;
     const int pitch = row_pitch(width);
-    const int groups = launcher_rest ? 1 : forward_groups(num_rois, nchunks);
+    const int groups = P.groups;
+    const bool launcher_rest = P.launcher;
 
     // prologue: relayout + affine table in one launch
     if (stages & RROI_STAGE_PROLOGUE) {
@@ -839,10 +1185,8 @@ static int forward_impl(const float* features, int feature_layout, int top_layou
         if (st != 1) return st;
     }
     if (stages & RROI_STAGE_GATHER) {
-        const ForwardPlan plan = plan_forward_gather(num_rois, channels, NB, nchunks, out_nhwc, launcher_rest, groups,
-                                                     zero_copy ? (size_t)batch_size * HW * channels * 4 / 8 : ws.cm_bytes / 8);
+        const ForwardPlan& plan = P.gather;
         const int ntiles = plan.ntiles;
-        if ((long)num_rois * ntiles >= (1L << 31)) return 0;
         SliceLayout lay;
         if (zero_copy) {
             lay.px_bytes = (unsigned)channels * 4u;
@@ -875,6 +1219,22 @@ static int forward_impl(const float* features, int feature_layout, int top_layou
     return launch_status();
 }
 
+static int forward_impl(const float* features, int feature_layout, int top_layout, float spatial_scale,
+                        int batch_size, int num_rois, int height, int width, int channels,
+                        int pooled_height, int pooled_width, const float* rois, float* top_data,
+                        void* workspace, size_t workspace_bytes, int path, int stages, void* stream_)
+{
+    if ((stages & ~RROI_STAGE_ALL) || stages == 0) return 0;
+    const FwdDispatch P = plan_forward(feature_layout, top_layout, batch_size, num_rois, height, width, channels,
+                                       pooled_height, pooled_width, path, RROI_CALLER_NATIVE);
+    if (!P.status) return 0;
+    if (P.family == RROI_PLAN_NONE) return 1;
+    if (!features || !rois || !top_data) return 0;
+    return launch_forward(P, features, feature_layout, spatial_scale, batch_size, num_rois, height, width, channels,
+                          pooled_height, pooled_width, rois, top_data, nullptr, nullptr, workspace, workspace_bytes,
+                          stages, static_cast<hipStream_t>(stream_));
+}
+
 int rroi_align_backward_hip(const float* top_diff, float spatial_scale, int batch_size,
                             int num_rois, int height, int width, int channels,
                             int pooled_height, int pooled_width, const float* rois,
@@ -890,7 +1250,7 @@ int rroi_align_backward_hip(const float* top_diff, float spatial_scale, int batc
 static int backward_impl(const float* top_diff, int top_diff_layout, int bottom_diff_layout,
                          float spatial_scale, int batch_size, int num_rois, int height, int width, int channels,
                          int pooled_height, int pooled_width, const float* rois, float* bottom_diff,
-                         void* workspace, size_t workspace_bytes, int path, void* stream_, bool accumulate);
+                         void* workspace, size_t workspace_bytes, int path, void* stream_);
 
 int rroi_align_backward_layout_hip(const float* top_diff, int top_diff_layout, int bottom_diff_layout,
                                    float spatial_scale, int batch_size, int num_rois, int height,
@@ -900,105 +1260,51 @@ int rroi_align_backward_layout_hip(const float* top_diff, int top_diff_layout, i
 {
     return backward_impl(top_diff, top_diff_layout, bottom_diff_layout, spatial_scale, batch_size, num_rois, height,
                          width, channels, pooled_height, pooled_width, rois, bottom_diff, workspace, workspace_bytes,
-                         path, stream_, false);
+                         path, stream_);
 }
 
-// accumulate (the reference-ABI launcher, tiled NCHW paths only): bottom_diff += gradient instead of = gradient
-// AUTO / TILED choose among the gathers; LISTS and INKERNEL name one
-static inline bool gather_choice_is_open(int path)
+// Launches the plan `P` (plan_backward on the same arguments); P.accumulate: bottom_diff += gradient.
+static int launch_backward(const BwdDispatch& P, const float* top_diff, float spatial_scale, int batch_size, int num_rois,
+                           int height, int width, int channels, int pooled_height, int pooled_width, const float* rois,
+                           float* bottom_diff, void* workspace, size_t workspace_bytes, hipStream_t stream)
 {
-    return path != RROI_PATH_TILED_LISTS && path != RROI_PATH_TILED_INKERNEL;
-}
-
-static int backward_impl(const float* top_diff, int top_diff_layout, int bottom_diff_layout,
-                         float spatial_scale, int batch_size, int num_rois, int height, int width, int channels,
-                         int pooled_height, int pooled_width, const float* rois, float* bottom_diff,
-                         void* workspace, size_t workspace_bytes, int path, void* stream_, bool accumulate)
-{
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (path & ~(0xff | RROI_PATH_TRIG_FP32)) return 0;   // unknown flag bits
-    const int trig = (path & RROI_PATH_TRIG_FP32) ? RROI_TRIG_FP32 : RROI_TRIG_DOUBLE;
-    path &= 0xff;
-    if (top_diff_layout != RROI_LAYOUT_NCHW && top_diff_layout != RROI_LAYOUT_NHWC) return 0;
-    if (bottom_diff_layout != RROI_LAYOUT_NCHW && bottom_diff_layout != RROI_LAYOUT_NHWC) return 0;
-    const bool td_nhwc = top_diff_layout == RROI_LAYOUT_NHWC, bd_nhwc = bottom_diff_layout == RROI_LAYOUT_NHWC;
-    // channels-last tensors are read / written in place by the gather formulation only
-    if ((td_nhwc || bd_nhwc) &&
-        (channels % 4 != 0 || path == RROI_PATH_DIRECT || path == RROI_PATH_TILED_ATOMIC))
-        return 0;
-    if (!shape_ok(batch_size, num_rois, height, width, channels, pooled_height, pooled_width))
-        return 0;
-    if (path != RROI_PATH_AUTO && path != RROI_PATH_DIRECT && path != RROI_PATH_TILED &&
-        path != RROI_PATH_TILED_ATOMIC && path != RROI_PATH_TILED_LISTS && path != RROI_PATH_TILED_INKERNEL &&
-        path != RROI_PATH_TILED_BUCKETS)
-        return 0;
-    if (!bottom_diff) return 0;
+    const int trig = P.trig;
     const int NB = pooled_height * pooled_width;
     const size_t HW = (size_t)height * width;
     const size_t in_bytes = (size_t)batch_size * channels * HW * sizeof(float);
-    if (num_rois == 0) return status_of(hipMemsetAsync(bottom_diff, 0, in_bytes, stream));
-    if (!top_diff || !rois) return 0;
-
-    const bool tiled = td_nhwc || bd_nhwc || (path == RROI_PATH_AUTO
-                                       ? pick_tiled_bwd(batch_size, channels, height, width, num_rois, NB)
-                                       : path != RROI_PATH_DIRECT);
-    if (accumulate && (!tiled || bd_nhwc)) return 0;
-    if (!tiled) {
+    const bool td_nhwc = P.td_nhwc, bd_nhwc = P.bd_nhwc, accumulate = P.accumulate;
+    switch (P.family) {
+    case RROI_PLAN_NONE:
+        return accumulate ? 1 : status_of(hipMemsetAsync(bottom_diff, 0, in_bytes, stream));
+    case RROI_PLAN_BWD_DIRECT: {
         hipError_t e = hipMemsetAsync(bottom_diff, 0, in_bytes, stream);
         if (e != hipSuccess) return status_of(e);
-        dim3 grid;
-        int cslab;
-        direct_grid(num_rois, NB, channels, grid, cslab);
-        hipLaunchKernelGGL(rroi_bwd_direct_kernel, grid, dim3(256), 0, stream, top_diff, rois,
+        hipLaunchKernelGGL(rroi_bwd_direct_kernel, P.grid, dim3(256), 0, stream, top_diff, rois,
                            bottom_diff, num_rois, channels, height, width, pooled_height,
-                           pooled_width, spatial_scale, trig, batch_size, cslab);
+                           pooled_width, spatial_scale, trig, batch_size, P.cslab);
         return launch_status();
+    }
+    case RROI_PLAN_BWD_ATOMIC:
+    case RROI_PLAN_BWD_INKERNEL:
+    case RROI_PLAN_BWD_LISTS:
+    case RROI_PLAN_BWD_BUCKETS:
+        break;
+    default:   // (the literal kernel is the launcher's own)
+        return 0;
     }
 
     const BwdWorkspace ws = carve_bwd(workspace, batch_size, channels, height, width, num_rois, NB);
     if (!workspace || workspace_bytes < ws.bytes) return 0;
-    if ((td_nhwc || bd_nhwc) && (!ws.gather_ok || (size_t)num_rois * NB >= (1ull << 32))) return 0;
-    const int nchunks = ceil_div(channels, kChunk);
+    const int nchunks = P.nchunks;
     const int pitch = row_pitch(width);
     const int ptiles = ceil_div((long)HW, kRelayoutPx);
-    const bool gather = path != RROI_PATH_TILED_ATOMIC && ws.gather_ok;
-    // Two gathers.  K3t builds the pixel lists inside the gather kernel (rroi_backward_tile_kernels.h), K3g
-    // with count / scan / fill launches in HBM.  Measured (tools/crossover.py, MI355X, us per call,
-    // K3t / K3g): C = 64, 176x320 map, 11x96: R = 4 26 / 33, 32 31 / 37, 128 41 / 49, 512 88 / 98;  C = 64,
-    // 8 images of 160x160, 11x100: 45 / 51, 54 / 54, 68 / 72, 133 / 148;  C = 256, 160x160, 8x64: 39 / 39,
-    // 43 / 40, 77 / 62, 201 / 168 -- K3t's serial work per tile is hidden when a lane carries two
-    // channel chunks, not when it carries eight.  K3t addresses its source with 32-bit byte offsets.
-    const size_t src_bytes = td_nhwc ? (size_t)num_rois * NB * channels * 4
-                                     : (size_t)num_rois * NB * nchunks * kLineBytes;
-    const bool inkernel_ok = src_bytes < (1ull << 32);
-    if (path == RROI_PATH_TILED_INKERNEL && !(gather && inkernel_ok)) return 0;
-    // ... with four chunks per lane (C <= 128) it still wins where the lists are short: C = 128, 160x160,
-    // 8x64: R = 32 33 / 42, 128 48 / 48, 512 101 / 93;  C = 96, 176x320, 11x96: 38 / 45, 56 / 61, 114 / 122
-    const bool short_lists = (double)num_rois * NB <= 8.0 * (double)batch_size * HW;   // bins per map pixel
-    // every map tile's workgroup scans ALL the ROIs (in batches of 256): O(tiles x R), measured up to R = 512
-    // and 8 images -- beyond that the lists in HBM, whose cost does not grow that way, are the safe choice
-    const bool scan_ok = (double)num_rois * batch_size <= 8192.0;
-    // round 3 (profiles/r03_crossover.txt): up to 256 channels it also wins while there is at most one bin per map
-    // pixel -- C = 256, 160 x 160, 8 x 64: R = 4 45.9 / 52.8, 16 49.5 / 52.5, 32 49.7 / 53.7, 64 56.9 / 57.4, 128 78.3 / 65.5
-    const bool very_short = (double)num_rois * NB <= 1.0 * (double)batch_size * HW;
-    const bool prefer_inkernel = scan_ok && (nchunks <= 2 || (nchunks <= 4 && short_lists) || (nchunks <= 8 && very_short));
-    if (path == RROI_PATH_TILED_BUCKETS && !(gather && ws.bucket_ok)) return 0;
-    // Round 3: the lists in HBM built in ONE pass over the bins (fixed buckets of 2^kshift entries per pixel plus
-    // overflow chains, rroi_backward_kernels.h) instead of count / scan / fill.  Measured (tools/crossover.py,
-    // tools/bucket_ab.py, profiles/r03_crossover_buckets.txt; us per call, buckets / exact lists / K3t): cfg3 129 /
-    // 144 / 179;  C = 256 R = 16 37 / 53 / 48;  C = 64 176x320 R = 128 40 / 48 / 43;  8 images of 160x160 R = 64
-    // 49 / 61 / 61 -- they win wherever the bucket holds at least the average list (128 entries per pixel in buckets
-    // of 128: 74 / 89 / 164) and lose where most of a list lives in the chains (512 per pixel in buckets of 128:
-    // 200 / 128 / 318): the bucket grows with the density as far as carve_bwd's cap lets it, bucket_pref says if
-    // that was far enough.
-    const bool buckets = gather && ws.bucket_ok && gather_choice_is_open(path) &&
-                         (path == RROI_PATH_TILED_BUCKETS || (ws.bucket_pref && g_tune.bwd_buckets));
-    const bool lists = buckets || path == RROI_PATH_TILED_LISTS || !inkernel_ok ||
-                       (path != RROI_PATH_TILED_INKERNEL && !prefer_inkernel);
+    const bool gather = P.family != RROI_PLAN_BWD_ATOMIC;
+    const bool buckets = P.family == RROI_PLAN_BWD_BUCKETS;
+    const bool lists = buckets || P.family == RROI_PLAN_BWD_LISTS;
     const BucketLists BL = {ws.kshift, reinterpret_cast<int*>(ws.off), ws.bsum, ws.ov};
     {
         // affine table; the list passes' pixel counters (K3g) are cleared by the same launch
-        const unsigned nzero = gather && lists ? ws.keys.keys : 0u;
+        const unsigned nzero = lists ? ws.keys.keys : 0u;
         int ablocks = ceil_div(num_rois, 256);
         const int zblocks = nzero ? (int)std::min<long>(ceil_div((long)nzero, 1024), 2L * num_cus()) : 0;
         if (zblocks > ablocks) ablocks = zblocks;
@@ -1009,7 +1315,7 @@ static int backward_impl(const float* top_diff, int top_diff_layout, int bottom_
     int st = launch_status();
     if (st != 1) return st;
 
-    if (gather && !lists) {
+    if (P.family == RROI_PLAN_BWD_INKERNEL) {
         // K3t: relayout of top_diff (one launch, masked bins skipped), then the tile gather
         const KeyLayout KL = ws.keys;
         // a list entry names a bin; its chunk k is the 128-byte line at entry * line_stride + k * 32 floats:
@@ -1020,13 +1326,9 @@ static int backward_impl(const float* top_diff, int top_diff_layout, int bottom_
         const FastDiv dpw = make_fastdiv((unsigned)pooled_width);
         const PatchMap dnb = make_patch_map(pooled_height, pooled_width);
         if (!td_nhwc) {
-            const int tt = ceil_div(NB, kRelayoutPx);
-            const long tiles = (long)tt * nchunks * num_rois;
-            if (tiles >= (1L << 31)) return 0;
-            // one block per pixel range (all its chunks), at most 8 resident blocks per CU
-            long blocks = tiles / nchunks;
-            const long cap = (long)num_cus() * 8;
-            if (blocks > cap) blocks = cap;
+            const int tt = P.tt;
+            const long tiles = P.tiles;
+            const long blocks = P.relayout_blocks;
 #define RROI_LAUNCH_R(SAUX)                                                                              \
     hipLaunchKernelGGL((rroi_bwd_pairs_relayout_kernel<0, SAUX>), dim3((unsigned)blocks), dim3(256), 0,       \
                        stream, ws.aff, num_rois, height, width, pooled_width, NB, batch_size, lines_per_roi, \
@@ -1039,23 +1341,23 @@ static int backward_impl(const float* top_diff, int top_diff_layout, int bottom_
             if (st != 1) return st;
         }
         const unsigned ntiles = KL.keys / 32u;
-        const unsigned per_xcd = (ntiles + 7u) / 8u;
+        const unsigned per_xcd = P.grid.x / 8u;
         const FastDiv dbt = make_fastdiv(KL.Ht * KL.Wt), dwt = make_fastdiv(KL.Wt), dph = make_fastdiv((unsigned)pooled_height);
         float* dst = bd_nhwc ? bottom_diff : ws.gcm;
         const float* srcT = td_nhwc ? top_diff : ws.tdT;
 #define RROI_LAUNCH_TG(NK, NHWC)                                                                          \
-    hipLaunchKernelGGL((rroi_bwd_tile_gather_kernel<NK, NHWC>), dim3(per_xcd * 8u), dim3(kTgThreads), 0, stream, \
+    hipLaunchKernelGGL((rroi_bwd_tile_gather_kernel<NK, NHWC>), P.grid, dim3(kTgThreads), 0, stream,         \
                        srcT, ws.aff, dst, num_rois, channels, height, width, pitch, pooled_height,           \
                        pooled_width, batch_size, nchunks, chunk_stride, line_stride, lines_per_roi, KL,      \
                        ntiles, per_xcd, dbt, dwt, dph)
 #define RROI_LAUNCH_TG_NK(NHWC)                          \
     do {                                                 \
-        if (nchunks > 4) RROI_LAUNCH_TG(8, NHWC);        \
-        else if (nchunks > 2) RROI_LAUNCH_TG(4, NHWC);   \
-        else if (nchunks > 1) RROI_LAUNCH_TG(2, NHWC);   \
+        if (P.nk == 8) RROI_LAUNCH_TG(8, NHWC);          \
+        else if (P.nk == 4) RROI_LAUNCH_TG(4, NHWC);     \
+        else if (P.nk == 2) RROI_LAUNCH_TG(2, NHWC);     \
         else RROI_LAUNCH_TG(1, NHWC);                    \
     } while (0)
-        if (bd_nhwc) {
+        if (P.dest == RROI_PLAN_DST_NHWC) {
             RROI_LAUNCH_TG_NK(true);
             return launch_status();  // written in place: no relayout back
         }
@@ -1068,48 +1370,19 @@ static int backward_impl(const float* top_diff, int top_diff_layout, int bottom_
     if (gather) {
         // (1) pixel -> (bin, weight) lists: count, scan, fill
         const KeyLayout KL = ws.keys;
-        // few scan blocks: every consumer block prefix-sums their totals itself (no second scan launch)
-        const int raw_bsum = ws.scan_blocks <= kInlineScanBlocks ? 1 : 0;
+        const int raw_bsum = P.raw_bsum;
         // a list entry names a bin; its chunk k is the 128-byte line at entry * line_stride + k * 32 floats:
         // in the relaid-out copy (R, NB, nchunks * 32) or in a channels-last top_diff (R, NB, C) consumed in place
         const unsigned lines_per_roi = (unsigned)NB;
         const unsigned chunk_stride = (unsigned)kChunk;
         const unsigned line_stride = td_nhwc ? (unsigned)channels : (unsigned)nchunks * (unsigned)kChunk;
-        // one pair block per CU, looping over the bins: the pair passes need outstanding atomics,
-        // not CU slots -- more blocks only take residency from the relayout (207 -> 197 us per call)
         const FastDiv dpw = make_fastdiv((unsigned)pooled_width);
         const PatchMap dnb = make_patch_map(pooled_height, pooled_width);
-        if ((long)num_rois * dnb.lanes_per_roi >= (1L << 32)) return 0;
-        int pblocks = ceil_div((long)num_rois * dnb.lanes_per_roi, 256);
-        {
-            // pair blocks per CU.  A pair wave walks a chain of returning atomics (~2.5 us per patch of 64 bins under
-            // load), so its launch time is patches per wave x that; the relayout it shares the launch with takes
-            // bytes / bandwidth.  One block per CU hides the pairs behind the relayout of 256 channels (round 2); with
-            // FEWER channels the same bins bring a quarter of the bytes and the pair pass set the launch (R = 512, C = 64,
-            // 11 x 96: 58 us where the relayout alone takes 30): blocks per CU ~ 256 / C.
-            // (tools/pair_blocks_ab.py, profiles/r05_pair_blocks_ab2.txt: with the wave-aggregated reservations, us per call at 1 / 2
-            // / 4 / 8 blocks per CU -- C = 64, R = 512, 11 x 96: 90.6 / 73.0 / 67.0 / 68.8 (round 4: 84.3); C = 128: 66.5 / 58.9 /
-            // 59.7 / 59.7; configs[2]: 104.4 / 103.3 / 103.6 / 103.5)
-            int per_cu = g_tune.bwd_pair_blocks_per_cu;
-            if (per_cu <= 0) per_cu = std::min(4, std::max(2, 256 / std::max(channels, 1)));
-            // channels-last gradients need no relayout: the pair blocks have the launch to themselves (CL=1 tools/pair_blocks_ab.py,
-            // profiles/r05_pair_blocks_ab_cl.txt: C = 64, R = 512 45.3 / 41.4 us at 4 / 8 per CU, round 4: 64.0; configs[2] 52.8 / 49.0, 51.3)
-            if (g_tune.bwd_pair_blocks_per_cu <= 0 && td_nhwc) per_cu = 8;
-            const long cap = (long)num_cus() * per_cu;
-            if (pblocks > cap) pblocks = (int)cap;
-        }
-        // the bucket slots reserved per WAVE through a table in LDS (pairs_reserve_wave) -- where a wave has several
-        // patches to walk; with one patch per wave the table's set-up is pure latency (R = 32, C = 64: +0.8 us)
-        const bool aggregate = g_tune.bwd_pair_aggregate &&
-                               (long)num_rois * (dnb.lanes_per_roi / 64) > 8L * num_cus();
-        // count || first half of the relayout;  scan;  fill || second half.  The relayout is the
-        // forward's, with R "images" of PH x PW "pixels" and the masked bins skipped:
-        // top_diff (R, C, NB) -> (R, NB, nchunks * 32)
-        const int tt = ceil_div(NB, kRelayoutPx);
-        const long tiles = td_nhwc ? 0 : (long)tt * nchunks * num_rois;  // nothing to relay out
-        if (tiles >= (1L << 31)) return 0;
+        const int pblocks = P.pblocks;
+        const bool aggregate = P.aggregate;
+        const int tt = P.tt;
+        const long tiles = P.tiles, half = P.half;
         const long unit = nchunks;  // a block takes all chunks of a pixel range: whole ranges per launch
-        const long half = (tiles / 2 + unit - 1) / unit * unit < tiles ? (tiles / 2 + unit - 1) / unit * unit : tiles;
         auto relayout_grid = [&](long n) {   // n tiles -> blocks: one per pixel range, at most 8 resident per CU
             const long cap = (long)num_cus() * 8;
             return n / unit <= cap ? n / unit : cap;
@@ -1141,48 +1414,29 @@ static int backward_impl(const float* top_diff, int top_diff_layout, int bottom_
         st = launch_status();
         if (st != 1) return st;
         // (3) gather: one thread group per key, no grid-stride
-        unsigned sub_shift = 3;  // 8 lanes = one chunk
-        while ((1u << sub_shift) < 8u * (unsigned)nchunks && sub_shift < 6) ++sub_shift;
-        // NCHW bottom_diff written in place (round 4; tools/bwd_nchw_ab.py, profiles/r04_bwd_nchw_ab.txt): a workgroup
-        // needs whole rows (8 pixels) of a key tile, i.e. at most 32 lanes per pixel -- wider pixels (C > 128) deal
-        // their passes of four chunks to blockIdx.y, which walks every list once per pass: that pays while the lists
-        // are short (cfg3, 10 bins per map pixel: 125.6 -> 117.5 us; 20 per pixel: 274 -> 283), so C > 128 keeps the
-        // scratch form beyond 16 bins per pixel.  C <= 128 gains at every density measured: R = 512, C = 64 / 128
-        // 76.0 -> 71.9 / 76.5 -> 71.2, R = 16...32 36.8 -> 29.0 / 24.3 -> 17.9 (the relayout launch was a fifth of
-        // those calls), 84 bins per pixel 159 -> 153.
-        const bool nchw_direct = !bd_nhwc && g_tune.bwd_nchw_direct != 0 &&
-                                 (nchunks <= 4 || (double)num_rois * NB <= (double)g_tune.bwd_nchw_direct * (double)batch_size * HW);
-        unsigned gy = 1;
-        if (nchw_direct && sub_shift == 6) {
-            sub_shift = 5;
-            gy = (unsigned)ceil_div(nchunks, 4);
-        }
-        const unsigned groups_per_block = 256u >> sub_shift;
-        // whole groups of 8 key tiles (the kernel deals the tiles of a group to the 8 XCDs)
-        const long wg_per_tile = 32 / groups_per_block;  // 1, 2, 4 or 8
-        const unsigned tile_run = nchw_direct ? (unsigned)g_tune.bwd_tile_run : 0u;
-        const long gblocks = ceil_div(ceil_div((long)KL.keys, 32L), 8L << tile_run) * (8L << tile_run) * wg_per_tile;
+        const unsigned sub_shift = P.sub_shift, tile_run = P.tile_run;
         // the lists: count / scan / fill segments (`off` = scanned offsets) or buckets (`off` = the counters)
         const unsigned* loff = buckets ? reinterpret_cast<const unsigned*>(ws.cnt) : ws.off;
 #define RROI_LAUNCH_G(DSTK, BUCK, DST)                                                                        \
-    hipLaunchKernelGGL((rroi_bwd_gather_kernel<DSTK, BUCK>), dim3((unsigned)gblocks, gy), dim3(256), 0, stream, \
+    hipLaunchKernelGGL((rroi_bwd_gather_kernel<DSTK, BUCK>), P.grid, dim3(256), 0, stream,                    \
                        td_nhwc ? top_diff : ws.tdT, loff, ws.bsum, ws.pairs, DST, channels, height, width,    \
                        pitch, nchunks, chunk_stride, line_stride, sub_shift, KL, make_fastdiv(KL.Ht * KL.Wt), \
                        make_fastdiv(KL.Wt), ws.scan_blocks, raw_bsum, BL, tile_run)
-        if (bd_nhwc) {
+        switch (P.dest) {
+        case RROI_PLAN_DST_NHWC:   // written in place: no relayout back
             if (buckets) RROI_LAUNCH_G(kDstNhwc, true, bottom_diff);
             else RROI_LAUNCH_G(kDstNhwc, false, bottom_diff);
-            return launch_status();  // written in place: no relayout back
-        }
-        if (nchw_direct) {
-            if (accumulate) {
-                if (buckets) RROI_LAUNCH_G(kDstNchwAdd, true, bottom_diff);
-                else RROI_LAUNCH_G(kDstNchwAdd, false, bottom_diff);
-            } else {
-                if (buckets) RROI_LAUNCH_G(kDstNchw, true, bottom_diff);
-                else RROI_LAUNCH_G(kDstNchw, false, bottom_diff);
-            }
-            return launch_status();  // written in place
+            return launch_status();
+        case RROI_PLAN_DST_NCHW_ADD:
+            if (buckets) RROI_LAUNCH_G(kDstNchwAdd, true, bottom_diff);
+            else RROI_LAUNCH_G(kDstNchwAdd, false, bottom_diff);
+            return launch_status();
+        case RROI_PLAN_DST_NCHW:
+            if (buckets) RROI_LAUNCH_G(kDstNchw, true, bottom_diff);
+            else RROI_LAUNCH_G(kDstNchw, false, bottom_diff);
+            return launch_status();
+        default:
+            break;
         }
         if (buckets) RROI_LAUNCH_G(kDstChunkMajor, true, ws.gcm);
         else RROI_LAUNCH_G(kDstChunkMajor, false, ws.gcm);
@@ -1192,16 +1446,14 @@ static int backward_impl(const float* top_diff, int top_diff_layout, int bottom_
     } else {
         hipError_t e = hipMemsetAsync(ws.gcm, 0, (size_t)batch_size * nchunks * height * pitch * kLineBytes, stream);
         if (e != hipSuccess) return status_of(e);
-        const int ntiles = ceil_div(NB, kTileBins);
-        if ((long)num_rois * ntiles >= (1L << 31)) return 0;
-        const int grid = tiled_grid((long)num_rois * ntiles, nchunks);
+        const int ntiles = P.ntiles;
         const FastDiv dt = make_fastdiv((unsigned)ntiles), dp = make_fastdiv((unsigned)pooled_width);
-        if (NB % 4 == 0)
-            hipLaunchKernelGGL(rroi_bwd_tiled_kernel<true>, dim3(grid), dim3(kWave), 0, stream,
+        if (P.vec4)
+            hipLaunchKernelGGL(rroi_bwd_tiled_kernel<true>, P.grid, dim3(kWave), 0, stream,
                                top_diff, ws.aff, ws.gcm, num_rois, channels, height, width, pitch,
                                pooled_width, NB, batch_size, nchunks, ntiles, dt, dp);
         else
-            hipLaunchKernelGGL(rroi_bwd_tiled_kernel<false>, dim3(grid), dim3(kWave), 0, stream,
+            hipLaunchKernelGGL(rroi_bwd_tiled_kernel<false>, P.grid, dim3(kWave), 0, stream,
                                top_diff, ws.aff, ws.gcm, num_rois, channels, height, width, pitch,
                                pooled_width, NB, batch_size, nchunks, ntiles, dt, dp);
         st = launch_status();
@@ -1216,6 +1468,20 @@ static int backward_impl(const float* top_diff, int top_diff_layout, int bottom_
                            stream, ws.gcm, bottom_diff, channels, (int)HW, width, pitch,
                            make_fastdiv((unsigned)width), nchunks, ptiles);
     return launch_status();
+}
+
+static int backward_impl(const float* top_diff, int top_diff_layout, int bottom_diff_layout,
+                         float spatial_scale, int batch_size, int num_rois, int height, int width, int channels,
+                         int pooled_height, int pooled_width, const float* rois, float* bottom_diff,
+                         void* workspace, size_t workspace_bytes, int path, void* stream_)
+{
+    const BwdDispatch P = plan_backward(top_diff_layout, bottom_diff_layout, batch_size, num_rois, height, width, channels,
+                                        pooled_height, pooled_width, path, RROI_CALLER_NATIVE);
+    if (!P.status) return 0;
+    if (!bottom_diff) return 0;
+    if (P.family != RROI_PLAN_NONE && (!top_diff || !rois)) return 0;
+    return launch_backward(P, top_diff, spatial_scale, batch_size, num_rois, height, width, channels, pooled_height,
+                           pooled_width, rois, bottom_diff, workspace, workspace_bytes, static_cast<hipStream_t>(stream_));
 }
 
 int rroi_align_bin_centres_hip(float spatial_scale, int num_rois, int height, int width,
@@ -1374,24 +1640,17 @@ int RROIAlignForwardLaucher(const float* bottom_data, const float spatial_scale,
                             float* con_idx_y, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!shape_ok(1, num_rois, height, width, channels, pooled_height, pooled_width)) return 0;
-    if (num_rois == 0) return 1;
+    const FwdDispatch P = plan_forward(RROI_LAYOUT_NCHW, RROI_LAYOUT_NCHW, 1, num_rois, height, width, channels,
+                                       pooled_height, pooled_width, launcher_trig() ? RROI_PATH_TRIG_FP32 : 0,
+                                       con_idx_x ? RROI_CALLER_LAUNCHER_CON_IDX : RROI_CALLER_LAUNCHER);
+    if (!P.status) return 0;
+    if (P.family == RROI_PLAN_NONE) return 1;
     if (!bottom_data || !bottom_rois || !top_data) return 0;
     if ((con_idx_x == nullptr) != (con_idx_y == nullptr)) return 0;
-    const int NB = pooled_height * pooled_width;
-    dim3 grid;
-    int cslab;
-    direct_grid(num_rois, NB, channels, grid, cslab);
-    if (!pick_tiled_fwd(1, channels, height, width, num_rois, NB)) {
-        if (launch_patch_forward(bottom_data, bottom_rois, top_data, con_idx_x, con_idx_y, num_rois, channels, height, width,
-                                 pooled_height, pooled_width, spatial_scale, launcher_trig(), /*batch_size unknown*/ -1, stream))
-            return launch_status();
-        hipLaunchKernelGGL(rroi_fwd_direct_kernel, grid, dim3(256), 0, stream, bottom_data, bottom_rois,
-                           top_data, con_idx_x, con_idx_y, num_rois, channels, height, width,
-                           pooled_height, pooled_width, spatial_scale, launcher_trig(), /*batch_size unknown*/ -1,
-                           cslab);
-        return launch_status();
-    }
+    if (P.family != RROI_PLAN_FWD_TWO_LAUNCH)   // the direct kernels (no scratch) write con_idx themselves
+        return launch_forward(P, bottom_data, RROI_LAYOUT_NCHW, spatial_scale, 1, num_rois, height, width, channels,
+                              pooled_height, pooled_width, bottom_rois, top_data, con_idx_x, con_idx_y, nullptr, 0,
+                              RROI_STAGE_ALL, stream);
     // Tiled path for the ROIs of image 0 (every ROI, in inference and in the benchmark); the
     // signature does not say how many images `bottom_data` holds, so the ROIs of images >= 1 are
     // sampled from the NCHW tensor by one more block per ROI of the prologue launch (trusting the
@@ -1401,14 +1660,13 @@ int RROIAlignForwardLaucher(const float* bottom_data, const float spatial_scale,
     ScratchLease lease = launcher_scratch(stream, bytes);
     void* const ws = lease.ptr;
     if (!ws) return status_of(lease.err);
-    int st = forward_impl(bottom_data, RROI_LAYOUT_NCHW, RROI_LAYOUT_NCHW, spatial_scale, 1, num_rois, height,
-                          width, channels, pooled_height, pooled_width, bottom_rois, top_data, ws, bytes,
-                          RROI_PATH_TILED | (launcher_trig() ? RROI_PATH_TRIG_FP32 : 0), RROI_STAGE_ALL, stream_,
-                          /*launcher_rest*/ true);
-    if (st == 1 && con_idx_x) {
-        hipLaunchKernelGGL(rroi_con_idx_kernel, grid, dim3(256), 0, stream, bottom_rois, con_idx_x, con_idx_y,
-                           num_rois, channels, height, width, pooled_height, pooled_width, spatial_scale, launcher_trig(),
-                           cslab);
+    int st = launch_forward(P, bottom_data, RROI_LAYOUT_NCHW, spatial_scale, 1, num_rois, height, width, channels,
+                            pooled_height, pooled_width, bottom_rois, top_data, nullptr, nullptr, ws, bytes,
+                            RROI_STAGE_ALL, stream);
+    if (st == 1 && P.con_idx) {
+        hipLaunchKernelGGL(rroi_con_idx_kernel, P.dgrid, dim3(256), 0, stream, bottom_rois, con_idx_x, con_idx_y,
+                           num_rois, channels, height, width, pooled_height, pooled_width, spatial_scale, P.trig,
+                           P.cslab);
         st = launch_status();
     }
     const hipError_t e = lease.give_back(stream);   // (everything that uses the buffer is enqueued)
@@ -1428,31 +1686,63 @@ int RROIAlignBackwardLaucher(const float* top_diff, const float spatial_scale,
                              void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!shape_ok(batch_size, num_rois, height, width, channels, pooled_height, pooled_width))
-        return 0;
-    if (num_rois == 0) return 1;
+    const BwdDispatch P = plan_backward(RROI_LAYOUT_NCHW, RROI_LAYOUT_NCHW, batch_size, num_rois, height, width, channels,
+                                        pooled_height, pooled_width, launcher_trig() ? RROI_PATH_TRIG_FP32 : 0,
+                                        RROI_CALLER_LAUNCHER);
+    if (!P.status) return 0;
+    if (P.family == RROI_PLAN_NONE) return 1;
     if (!top_diff || !bottom_rois || !bottom_diff || !con_idx_x || !con_idx_y) return 0;
-    const int NB = pooled_height * pooled_width;
-    if (pick_tiled_bwd(batch_size, channels, height, width, num_rois, NB)) {
-        const size_t bytes = carve_bwd(nullptr, batch_size, channels, height, width, num_rois, NB).bytes;
+    if (P.family != RROI_PLAN_BWD_LITERAL) {
+        const size_t bytes = P.ws.bytes;
         ScratchLease lease = launcher_scratch(stream, bytes);
         void* const ws = lease.ptr;
         if (!ws) return status_of(lease.err);
-        const int st = backward_impl(top_diff, RROI_LAYOUT_NCHW, RROI_LAYOUT_NCHW, spatial_scale, batch_size, num_rois,
-                                     height, width, channels, pooled_height, pooled_width, bottom_rois, bottom_diff,
-                                     ws, bytes, RROI_PATH_TILED | (launcher_trig() ? RROI_PATH_TRIG_FP32 : 0), stream_,
-                                     /*accumulate*/ true);
+        const int st = launch_backward(P, top_diff, spatial_scale, batch_size, num_rois, height, width, channels,
+                                       pooled_height, pooled_width, bottom_rois, bottom_diff, ws, bytes, stream);
         const hipError_t e = lease.give_back(stream);
         return st != 1 ? st : status_of(e);
     }
     const long nthreads = (long)num_rois * pooled_height * pooled_width * channels;
-    long blocks = (nthreads + 255) / 256;
-    const long cap = (long)num_cus() * 32;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(rroi_bwd_literal_kernel, dim3((unsigned)blocks), dim3(256), 0, stream,
+    hipLaunchKernelGGL(rroi_bwd_literal_kernel, P.grid, dim3(256), 0, stream,
                        top_diff, con_idx_x, con_idx_y, bottom_rois, bottom_diff, nthreads, channels,
                        height, width, pooled_height, pooled_width);
     return launch_status();
+}
+
+// ---- the plan query (section 2 of the header) ----------------------------------------
+int rroi_align_forward_plan(int feature_layout, int top_layout, int batch_size, int num_rois, int height, int width,
+                            int channels, int pooled_height, int pooled_width, int path, int caller,
+                            rroi_align_plan* plan)
+{
+    if (!plan) return 0;
+    const FwdDispatch P = plan_forward(feature_layout, top_layout, batch_size, num_rois, height, width, channels,
+                                       pooled_height, pooled_width, path, caller);
+    if (!P.status) return 0;
+    const bool gathers = P.family == RROI_PLAN_FWD_FUSED_STRIDED || P.family == RROI_PLAN_FWD_FUSED_SHIFT ||
+                         P.family == RROI_PLAN_FWD_TWO_LAUNCH;
+    const dim3 grid = gathers ? dim3(P.gather.grid)
+                      : P.family == RROI_PLAN_FWD_DIRECT_K2P ? P.patch.grid
+                      : P.family == RROI_PLAN_FWD_DIRECT_THREAD ? P.dgrid : dim3(0, 0, 0);
+    fill_plan(plan, P.family, gathers ? (int)P.gather.kernel : -1, P.family == RROI_PLAN_NONE ? 0 : P.groups,
+              gathers ? P.gather.ntiles : 0, grid, P.zero_copy, P.con_idx && P.family != RROI_PLAN_NONE, 0, 0, -1, 0,
+              RROI_PLAN_DST_NONE, false, false);
+    return 1;
+}
+
+int rroi_align_backward_plan(int top_diff_layout, int bottom_diff_layout, int batch_size, int num_rois, int height,
+                             int width, int channels, int pooled_height, int pooled_width, int path, int caller,
+                             rroi_align_plan* plan)
+{
+    if (!plan) return 0;
+    const BwdDispatch P = plan_backward(top_diff_layout, bottom_diff_layout, batch_size, num_rois, height, width, channels,
+                                        pooled_height, pooled_width, path, caller);
+    if (!P.status) return 0;
+    const bool lists = P.family == RROI_PLAN_BWD_LISTS || P.family == RROI_PLAN_BWD_BUCKETS;
+    fill_plan(plan, P.family, -1, 0, P.family == RROI_PLAN_BWD_ATOMIC ? P.ntiles : 0,
+              P.family == RROI_PLAN_NONE ? dim3(0, 0, 0) : P.grid, P.td_nhwc && P.family != RROI_PLAN_NONE, false, P.nk,
+              P.family == RROI_PLAN_BWD_BUCKETS ? (int)P.ws.kshift : 0, lists ? P.raw_bsum : -1, lists ? (int)P.gy : 0,
+              P.dest, P.accumulate && P.family != RROI_PLAN_NONE, P.vec4);
+    return 1;
 }
 
 int rroi_align_set_trig_recipe_hip(int recipe) { return recipe == RROI_TRIG_DOUBLE ? 1 : 0; }   // deprecated shim, see the header

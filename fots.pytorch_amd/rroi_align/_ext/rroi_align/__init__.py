@@ -31,6 +31,14 @@ STAGE_PROLOGUE, STAGE_GATHER, STAGE_ALL = 1, 2, 3
 # every value `path` may take in forward() (the parity tests run them all)
 FORWARD_PATHS = (PATH_AUTO, PATH_DIRECT, PATH_TILED, PATH_FUSED)
 
+# the plan query (include/rroi_align_hip.h section 2): callers, plan families, gather kernels, backward destinations
+CALLER_NATIVE, CALLER_LAUNCHER, CALLER_LAUNCHER_CON_IDX = 0, 1, 2
+PLAN_NONE = 0
+PLAN_FWD_DIRECT_K2P, PLAN_FWD_DIRECT_THREAD, PLAN_FWD_FUSED_STRIDED, PLAN_FWD_FUSED_SHIFT, PLAN_FWD_TWO_LAUNCH = 1, 2, 3, 4, 5
+PLAN_BWD_DIRECT, PLAN_BWD_ATOMIC, PLAN_BWD_INKERNEL, PLAN_BWD_LISTS, PLAN_BWD_BUCKETS, PLAN_BWD_LITERAL = 11, 12, 13, 14, 15, 16
+PLAN_KERNEL_STRIDED, PLAN_KERNEL_CHANNELS_LAST, PLAN_KERNEL_SHIFT, PLAN_KERNEL_STRIDED_MERGE, PLAN_KERNEL_SHIFT_LINES = 0, 1, 2, 3, 4
+PLAN_DST_NONE, PLAN_DST_CHUNK_MAJOR, PLAN_DST_NCHW, PLAN_DST_NCHW_ADD, PLAN_DST_NHWC = 0, 1, 2, 3, 4
+
 if not os.path.exists(LIB_PATH):
     raise ImportError(
         f"{LIB_PATH} is missing: build it with `make -C fots.pytorch_amd/csrc` "
@@ -87,6 +95,17 @@ _lib.rroi_align_release_launcher_scratch.argtypes = []
 _lib.rroi_align_launcher_scratch_stats.restype = _i
 _lib.rroi_align_launcher_scratch_stats.argtypes = [_vp, _vp, _vp, _vp]
 
+
+class _Plan(ctypes.Structure):
+    _fields_ = [(n, _i) for n in ("family", "kernel", "groups", "ntiles", "grid_x", "grid_y", "zero_copy", "con_idx", "nk",
+                                  "kshift", "raw_bsum", "gy", "dest", "accumulate", "vec4")]
+
+
+_lib.rroi_align_forward_plan.restype = _i
+_lib.rroi_align_forward_plan.argtypes = [_i] * 11 + [ctypes.POINTER(_Plan)]
+_lib.rroi_align_backward_plan.restype = _i
+_lib.rroi_align_backward_plan.argtypes = [_i] * 11 + [ctypes.POINTER(_Plan)]
+
 EXPORTS = (
     "RROIAlignForwardLaucher", "RROIAlignBackwardLaucher", "rroi_align_forward_hip",
     "rroi_align_backward_hip", "rroi_align_forward_stages_hip", "rroi_align_forward_workspace_bytes",
@@ -97,7 +116,38 @@ EXPORTS = (
     "rroi_align_release_launcher_scratch", "rroi_align_bin_centres_trig_hip", "rroi_nms_record_format",
     "rroi_align_write_probe_hip", "rroi_align_launcher_scratch_stats",
     "rroi_align_set_trig_recipe_hip", "rroi_align_get_trig_recipe_hip",   # deprecated shims (refuse TRIG_FP32)
+    "rroi_align_forward_plan", "rroi_align_backward_plan",
 )
+
+# What a call launches (rroi_align_forward_plan / rroi_align_backward_plan); the fields of rroi_align_plan.
+Plan = collections.namedtuple("Plan", [n for n, _ in _Plan._fields_])
+
+
+def _plan(fn, args, what):
+    p = _Plan()
+    if fn(*(int(a) for a in args), ctypes.byref(p)) != 1:
+        raise ValueError(f"{what}: the call would refuse these arguments")
+    return Plan(*(getattr(p, n) for n in Plan._fields))
+
+
+def forward_plan(batch_size, channels, height, width, num_rois, pooled_height, pooled_width,
+                 feature_layout=LAYOUT_NCHW, top_layout=LAYOUT_NCHW, path=PATH_AUTO, caller=CALLER_NATIVE,
+                 trig=0) -> Plan:
+    """The plan a forward call with these arguments runs (host only, no GPU needed); ValueError where the call
+    would refuse them."""
+    return _plan(_lib.rroi_align_forward_plan,
+                 (feature_layout, top_layout, batch_size, num_rois, height, width, channels, pooled_height, pooled_width,
+                  _path_word(path, trig), caller), "rroi_align_forward_plan")
+
+
+def backward_plan(batch_size, channels, height, width, num_rois, pooled_height, pooled_width,
+                  top_diff_layout=LAYOUT_NCHW, bottom_diff_layout=LAYOUT_NCHW, path=PATH_AUTO, caller=CALLER_NATIVE,
+                  trig=0) -> Plan:
+    """The plan a backward call with these arguments runs (host only, no GPU needed); ValueError where the call
+    would refuse them."""
+    return _plan(_lib.rroi_align_backward_plan,
+                 (top_diff_layout, bottom_diff_layout, batch_size, num_rois, height, width, channels, pooled_height,
+                  pooled_width, _path_word(path, trig), caller), "rroi_align_backward_plan")
 
 
 def version() -> str:

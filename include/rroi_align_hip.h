@@ -193,6 +193,67 @@ int rroi_align_backward_layout_hip(const float* top_diff, int top_diff_layout, i
                                    const float* rois, float* bottom_diff, void* workspace,
                                    size_t workspace_bytes, int path, void* stream);
 
+/* Plan query (0.9.0): what a call with these arguments WOULD launch -- host only: it launches nothing, touches no
+ * memory and needs no GPU (grids are sized for the current device's CU count, 256 where there is none).  The launches
+ * above run the same plan (one decision function per direction), so the answer cannot disagree with what runs.
+ * Arguments: those of rroi_align_forward_layout_hip / rroi_align_backward_layout_hip (path with its flag bits), and
+ * `caller`: RROI_CALLER_NATIVE = those entry points; RROI_CALLER_LAUNCHER = RROIAlignForwardLaucher with con_idx NULL
+ * / RROIAlignBackwardLaucher; RROI_CALLER_LAUNCHER_CON_IDX = RROIAlignForwardLaucher with con_idx (forward only).  A
+ * launcher call has NCHW layouts and path RROI_PATH_AUTO (| RROI_PATH_TRIG_FP32); the forward launcher ignores
+ * batch_size (its signature has none).  Returns 1 and fills *plan, or 0 exactly where the call would refuse its
+ * (non-pointer) arguments -- a workspace of the queried size assumed. */
+#define RROI_CALLER_NATIVE 0
+#define RROI_CALLER_LAUNCHER 1
+#define RROI_CALLER_LAUNCHER_CON_IDX 2
+/* plan.family */
+#define RROI_PLAN_NONE 0              /* no ROI: nothing launched (the native backward zeroes bottom_diff) */
+#define RROI_PLAN_FWD_DIRECT_K2P 1    /* rroi_fwd_patch_kernel                                            */
+#define RROI_PLAN_FWD_DIRECT_THREAD 2 /* rroi_fwd_direct_kernel, thread per bin (K2p does not apply)      */
+#define RROI_PLAN_FWD_FUSED_STRIDED 3 /* one launch from the NCHW map, strided tiles                      */
+#define RROI_PLAN_FWD_FUSED_SHIFT 4   /* one launch from the NCHW map, SHIFT tiles                        */
+#define RROI_PLAN_FWD_TWO_LAUNCH 5    /* prologue (relayout + affines) + the gather of plan.kernel        */
+#define RROI_PLAN_BWD_DIRECT 11       /* rroi_bwd_direct_kernel, atomics into NCHW                        */
+#define RROI_PLAN_BWD_ATOMIC 12       /* rroi_bwd_tiled_kernel<plan.vec4>, atomics into the chunk-major copy */
+#define RROI_PLAN_BWD_INKERNEL 13     /* rroi_bwd_tile_gather_kernel<plan.nk, NHWC>                       */
+#define RROI_PLAN_BWD_LISTS 14        /* count / scan (+ rroi_scan2_kernel where !plan.raw_bsum) / fill + gather */
+#define RROI_PLAN_BWD_BUCKETS 15      /* one-pass buckets of 1 << plan.kshift + overflow chains + gather  */
+#define RROI_PLAN_BWD_LITERAL 16      /* the backward launcher's per-element kernel (reads con_idx)       */
+/* plan.kernel: the gather instantiation of the fused / two-launch forward (-1: none) */
+#define RROI_PLAN_KERNEL_STRIDED 0
+#define RROI_PLAN_KERNEL_CHANNELS_LAST 1
+#define RROI_PLAN_KERNEL_SHIFT 2
+#define RROI_PLAN_KERNEL_STRIDED_MERGE 3
+#define RROI_PLAN_KERNEL_SHIFT_LINES 4
+/* plan.dest: where the backward's gradient goes */
+#define RROI_PLAN_DST_NONE 0
+#define RROI_PLAN_DST_CHUNK_MAJOR 1   /* scratch, then rroi_cm_to_nchw_kernel<plan.accumulate>            */
+#define RROI_PLAN_DST_NCHW 2          /* NCHW bottom_diff written in place                                */
+#define RROI_PLAN_DST_NCHW_ADD 3      /* NCHW bottom_diff added to in place                               */
+#define RROI_PLAN_DST_NHWC 4          /* channels-last bottom_diff written in place                       */
+typedef struct rroi_align_plan {
+    int family;     /* RROI_PLAN_* */
+    int kernel;     /* RROI_PLAN_KERNEL_*, -1 */
+    int groups;     /* forward: XCD groups (1 = off) */
+    int ntiles;     /* tiles per (roi, chunk) block of the tiled forward gather / the atomic backward; 0 */
+    int grid_x;     /* grid of the plan's main kernel (the gather; the direct kernel) */
+    int grid_y;
+    int zero_copy;  /* channels-last features (forward) / top_diff (backward) consumed in place */
+    int con_idx;    /* forward launcher: con_idx written */
+    int nk;         /* in-kernel backward: channel chunks per lane (1, 2, 4, 8); 0 */
+    int kshift;     /* buckets: log2 of the entries per bucket; 0 */
+    int raw_bsum;   /* lists / buckets: 1 = consumers prefix-sum the scan blocks' totals, 0 = rroi_scan2_kernel; -1 */
+    int gy;         /* list / bucket gather: channel passes in grid y (> 1: C > 128 on the in-place NCHW gather); 0 */
+    int dest;       /* RROI_PLAN_DST_* */
+    int accumulate; /* backward: added to bottom_diff */
+    int vec4;       /* atomic backward: rroi_bwd_tiled_kernel<true> (PH * PW % 4 == 0) */
+} rroi_align_plan;
+int rroi_align_forward_plan(int feature_layout, int top_layout, int batch_size, int num_rois, int height, int width,
+                            int channels, int pooled_height, int pooled_width, int path, int caller,
+                            rroi_align_plan* plan);
+int rroi_align_backward_plan(int top_diff_layout, int bottom_diff_layout, int batch_size, int num_rois, int height,
+                             int width, int channels, int pooled_height, int pooled_width, int path, int caller,
+                             rroi_align_plan* plan);
+
 /* ------------------------------------------------------------------------- *
  * 3. The callers' ROI construction, on the device.
  *    quads (n, 8) fp32 [x0,y0,x1,y1,x2,y2,x3,y3] -> rois (n, 6) fp32 rows for the
@@ -288,7 +349,7 @@ int rroi_align_write_probe_hip(float* out, size_t num_floats, void* stream);
 int rroi_align_set_trig_recipe_hip(int recipe);
 int rroi_align_get_trig_recipe_hip(void);
 
-/* Identification: "rroi_align_hip <version> gfx950" (0.7.0: per-call trig recipe, device-wide setter removed; 0.8.0: launcher scratch reused within a capture, table of 64, stats). */
+/* Identification: "rroi_align_hip <version> gfx950" (0.7.0: per-call trig recipe, device-wide setter removed; 0.8.0: launcher scratch reused within a capture, table of 64, stats; 0.9.0: plan query). */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus

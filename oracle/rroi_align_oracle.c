@@ -408,6 +408,68 @@ void rroi_oracle_backward_mt(const float* top_diff, float spatial_scale, int bat
     free(acc);
 }
 
+/*
+ * Per-element bound data for a backward under test: the same masks, taps and weights as rroi_oracle_backward, but
+ * for every feature element S = sum |w * g| (each fp32 product as the backward forms it, summed in double) and
+ * n = the number of terms that land on it.  Channel-partitioned over `threads` OpenMP threads as in
+ * rroi_oracle_backward_mt (the result does not depend on the thread count).  S and n are (B, C, H, W).
+ */
+void rroi_oracle_backward_bound(const float* top_diff, float spatial_scale, int batch_size, int num_rois,
+                                int height, int width, int channels, int pooled_height, int pooled_width,
+                                const float* bottom_rois, double* S, int* n_terms, int threads)
+{
+    const long plane_sz = (long)height * width;
+    const long total = (long)batch_size * channels * plane_sz;
+    const long bins = (long)pooled_height * pooled_width;
+    for (long i = 0; i < total; ++i) {
+        S[i] = 0.0;
+        n_terms[i] = 0;
+    }
+    if (threads < 1) threads = 1;
+#pragma omp parallel num_threads(threads)
+    {
+#ifdef _OPENMP
+        const int tid = omp_get_thread_num(), nt = omp_get_num_threads();
+#else
+        const int tid = 0, nt = 1;
+#endif
+        int* off = (int*)malloc((size_t)bins * 4 * sizeof(int));
+        float* wgt = (float*)malloc((size_t)bins * 4 * sizeof(float));
+        for (int n = 0; n < num_rois; ++n) {
+            rroi_affine_t A;
+            rroi_oracle_affine(bottom_rois + (long)n * 6, pooled_height, spatial_scale, &A);
+            if (A.batch < 0 || A.batch >= batch_size) continue;   /* no gradient (the product writes none) */
+            for (int ph = 0; ph < pooled_height; ++ph)
+                for (int pw = 0; pw < pooled_width; ++pw) {
+                    const long b = (long)ph * pooled_width + pw;
+                    float bin_cx, bin_cy;
+                    off[4 * b] = off[4 * b + 1] = off[4 * b + 2] = off[4 * b + 3] = -1;
+                    if (!bin_centre(&A, ph, pw, height, width, &bin_cx, &bin_cy)) continue;
+                    tap_weights(bin_cx, bin_cy, &wgt[4 * b], &wgt[4 * b + 1], &wgt[4 * b + 2], &wgt[4 * b + 3]);
+                    const int min_x = f2i_sat(floorf(bin_cx)), max_x = f2i_sat(ceilf(bin_cx));
+                    const int min_y = f2i_sat(floorf(bin_cy)), max_y = f2i_sat(ceilf(bin_cy));
+                    if (min_y > 0 && min_x > 0 && min_y < height - 1 && min_x < width - 1) off[4 * b] = min_y * width + min_x;
+                    if (min_y > 0 && max_x < width - 1 && min_y < height - 1 && max_x > 0) off[4 * b + 1] = min_y * width + max_x;
+                    if (max_y < height - 1 && max_x < width - 1 && max_y > 0 && max_x > 0) off[4 * b + 2] = max_y * width + max_x;
+                    if (max_y < height - 1 && min_x > 0 && max_y > 0 && min_x < width - 1) off[4 * b + 3] = max_y * width + min_x;
+                }
+            for (int c = tid; c < channels; c += nt) {
+                const float* g = top_diff + ((long)n * channels + c) * bins;
+                const long base = ((long)A.batch * channels + c) * plane_sz;
+                for (long b = 0; b < bins; ++b)
+                    for (int k = 0; k < 4; ++k) {
+                        const int o = off[4 * b + k];
+                        if (o < 0) continue;
+                        S[base + o] += fabs((double)(wgt[4 * b + k] * g[b]));
+                        n_terms[base + o] += 1;
+                    }
+            }
+        }
+        free(off);
+        free(wgt);
+    }
+}
+
 /* Number of distinct feature elements the forward reads (for bytes_feat in
  * SURVEY.md section 8(d)): counts (batch, y, x) taps that pass the validity
  * test of at least one active bin; multiply by channels*4 for bytes. */

@@ -129,6 +129,21 @@ def backward_c(grad_out, rois, feat_shape, scale, threads=None):
     return gin
 
 
+def backward_bound_c(grad_out, rois, feat_shape, scale, threads=8):
+    """Per-element data of the backward's error bound, on the masks and weights of backward_c: (S, n), both
+    (B, C, H, W) -- S = sum of |w * g| over the terms that land on the element (float64), n = their count (int32)."""
+    B, C, H, W = feat_shape
+    grad_out = np.ascontiguousarray(grad_out, np.float32)
+    rois = np.ascontiguousarray(rois, np.float32).reshape(-1, 6)
+    R, _, PH, PW = grad_out.shape
+    S = np.empty(feat_shape, np.float64)
+    n = np.empty(feat_shape, np.int32)
+    lib().rroi_oracle_backward_bound(_p(grad_out), ctypes.c_float(scale), B, R, H, W, C, PH, PW, _p(rois),
+                                     S.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                     n.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), int(threads))
+    return S, n
+
+
 def touched_pixels(rois, batch, H, W, pooled_h, pooled_w, scale) -> int:
     rois = np.ascontiguousarray(rois, np.float32).reshape(-1, 6)
     return int(lib().rroi_oracle_touched_pixels(ctypes.c_float(scale), batch, rois.shape[0], H, W,

@@ -142,7 +142,7 @@ def test_python_constants_are_the_headers():
     from rroi_align._ext import rroi_align as ext
     text = open(os.path.join(ROOT, "include", "rroi_align_hip.h")).read()
     defs = {m.group(1): int(m.group(2), 0)
-            for m in re.finditer(r"#define\s+RROI_((?:PATH|LAYOUT|TRIG)_\w+)\s+(0x[0-9a-fA-F]+|\d+)", text)}
+            for m in re.finditer(r"#define\s+RROI_((?:PATH|LAYOUT|TRIG|PLAN|CALLER)_\w+)\s+(0x[0-9a-fA-F]+|\d+)", text)}
     assert len(defs) >= 12 and "TRIG_FP32" in defs and defs["PATH_TRIG_FP32"] == 0x100
     for name, value in defs.items():
         assert getattr(ext, name) == value, name

@@ -269,6 +269,7 @@ def test_backward_vs_oracle(ext, oracle, name, path):
     # order of the sum alone moves the result by 1e-4 (measured 0.8 - 1.1e-4 = 4e-7 of the scale on every path, the
     # reference's unordered atomicAdds included): relative bar there
     Wk.check_backward(got, want, f"{name} {path}", require_abs=name != "c5_pad")
+    Wk.check_backward_elementwise(got, want, *oracle.backward_bound_c(gout, r, f.shape, s), what=f"{name} {path}")
     assert eq(got == 0, want == 0) or np.abs(got[(got == 0) != (want == 0)]).max() < 1e-30
 
 
@@ -278,9 +279,11 @@ def test_backward_edge_rois(ext, oracle):
     rois = np.concatenate([Wk.edge_rois(), Wk.degenerate_rois()[[0, 1, 2, 3, 4]]])
     gout = rng.standard_normal((len(rois), 8, 8, 64), dtype=np.float32)
     want = oracle.backward_c(gout, rois, f.shape, 0.25)
+    S, n = oracle.backward_bound_c(gout, rois, f.shape, 0.25)
     for p in (ext.PATH_DIRECT, ext.PATH_TILED, ext.PATH_TILED_LISTS, ext.PATH_TILED_BUCKETS, ext.PATH_TILED_INKERNEL, ext.PATH_TILED_ATOMIC):
         got = ext.backward(dev(gout), dev(rois), f.shape, 0.25, path=p).cpu().numpy()
         assert np.abs(got - want).max() <= BWD_RTOL * max(1.0, float(np.abs(want).max()))
+        Wk.check_backward_elementwise(got, want, S, n, what=f"edge rois path {p}")
 
 
 def test_backward_heavy_overlap(ext, oracle):
@@ -300,9 +303,11 @@ def test_backward_heavy_overlap(ext, oracle):
         rois[: R // 3] = rois[0]                      # identical copies
         gout = rng.standard_normal((R, C, ph, pw), dtype=np.float32)
         want = oracle.backward_c(gout, rois, f.shape, 0.25)
+        S, n = oracle.backward_bound_c(gout, rois, f.shape, 0.25)
         for p in (ext.PATH_TILED_LISTS, ext.PATH_TILED_BUCKETS, ext.PATH_TILED_INKERNEL, ext.PATH_TILED_ATOMIC):
             got = ext.backward(dev(gout), dev(rois), f.shape, 0.25, path=p).cpu().numpy()
             assert np.abs(got - want).max() <= BWD_RTOL * max(1.0, float(np.abs(want).max())), (R, p)
+            Wk.check_backward_elementwise(got, want, S, n, what=f"heavy overlap R={R} path {p}")
 
 
 def test_more_than_256_channels(ext, oracle):
@@ -558,14 +563,17 @@ def test_backward_channels_last_grad(ext, oracle, name):
     f, r, ph, pw, s = SHAPES[name]()
     gout = np.random.default_rng(3).standard_normal((len(r), f.shape[1], ph, pw)).astype(np.float32)
     want = oracle.backward_c(gout, r, f.shape, s)
+    S, n = oracle.backward_bound_c(gout, r, f.shape, s)
     G = dev(gout).contiguous(memory_format=torch.channels_last)
     assert not G.is_contiguous()
     for p in (ext.PATH_AUTO, ext.PATH_TILED, ext.PATH_TILED_LISTS, ext.PATH_TILED_BUCKETS, ext.PATH_TILED_INKERNEL):
         got = ext.backward(G, dev(r), f.shape, s, path=p).cpu().numpy()
         assert np.abs(got - want).max() <= BWD_RTOL * max(1.0, float(np.abs(want).max()))
+        Wk.check_backward_elementwise(got, want, S, n, what=f"channels-last grad {name} path {p}")
     # paths that need NCHW fall back to a contiguous copy
     got = ext.backward(G, dev(r), f.shape, s, path=ext.PATH_DIRECT).cpu().numpy()
     assert np.abs(got - want).max() <= BWD_RTOL * max(1.0, float(np.abs(want).max()))
+    Wk.check_backward_elementwise(got, want, S, n, what=f"channels-last grad {name} direct")
     # the C-ABI refuses the combinations it cannot serve
     R, C = gout.shape[:2]
     B, _, H, W = f.shape
@@ -935,9 +943,11 @@ def test_random_shape_sweep(ext, oracle):
             assert n == 0, f"trial {trial} C={C} {H}x{W} B={B} {ph}x{pw} s={s} R={R} path={p}: {n} differ (max {d})"
         gout = np.random.default_rng(trial).standard_normal(want.shape).astype(np.float32)
         gwant = oracle.backward_c(gout, r, f.shape, s)
+        S, n = oracle.backward_bound_c(gout, r, f.shape, s)
         for p in (ext.PATH_DIRECT, ext.PATH_TILED, ext.PATH_TILED_LISTS, ext.PATH_TILED_BUCKETS, ext.PATH_TILED_INKERNEL, ext.PATH_TILED_ATOMIC):
             g = ext.backward(dev(gout), dev(r), f.shape, s, path=p).cpu().numpy()
             assert np.abs(g - gwant).max() <= BWD_RTOL * max(1.0, float(np.abs(gwant).max())), f"trial {trial} bwd path={p}"
+            Wk.check_backward_elementwise(g, gwant, S, n, what=f"trial {trial} bwd path={p}")
 
 
 def test_views_with_storage_offsets(ext, oracle):
