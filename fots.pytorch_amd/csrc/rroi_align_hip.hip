@@ -36,6 +36,7 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "rroi_align_hip.h"
@@ -219,11 +220,16 @@ bool plan_patch_forward(int num_rois, int channels, int width, int pooled_height
     return true;
 }
 
-void launch_patch_forward(const PatchPlan& p, const float* features, const float* rois, float* top_data, float* idx_x,
+template <class T>
+void launch_patch_forward(const PatchPlan& p, const T* features, const float* rois, T* top_data, float* idx_x,
                           float* idx_y, int num_rois, int channels, int height, int width, int pooled_height, int pooled_width,
                           float spatial_scale, int trig, int batch_size, hipStream_t stream)
 {
-    if (idx_x)
+    if constexpr (!std::is_same<T, float>::value)   // (the reference ABI's con_idx: fp32 calls only)
+        hipLaunchKernelGGL((rroi_fwd_patch_kernel<4, false, T>), p.grid, dim3(256), 0, stream, features, rois, top_data, num_rois,
+                           channels, height, width, pooled_height, pooled_width, spatial_scale, trig, batch_size, p.cw, p.npx,
+                           p.npatches, p.prows, p.pcols, (float*)nullptr, (float*)nullptr);
+    else if (idx_x)
         hipLaunchKernelGGL((rroi_fwd_patch_kernel<4, true>), p.grid, dim3(256), 0, stream, features, rois, top_data, num_rois, channels,
                            height, width, pooled_height, pooled_width, spatial_scale, trig, batch_size, p.cw, p.npx, p.npatches,
                            p.prows, p.pcols, idx_x, idx_y);
@@ -463,8 +469,11 @@ constexpr int kShiftOwnBins = kTileBins - 16;   // bins a SHIFT tile advances by
 // allow_lines = false: the one-launch NCHW_SRC form has no SHIFT == 2 instantiation -- rows that are not whole sectors
 // take kShift there at any size (the plan used to return kShiftLines beyond 320 MB, which the fused launch
 // then ran as SHIFT = 0 on a grid sized for 32-bin tiles)
+// elem_bytes: bytes of one crop element (4, or 2 for bfloat16 / float16 crops).  The two rules below that stand for BYTES
+// of crops (the merging form from 48 MB, the line-aligned windows beyond the 320 MB memory-side cache) use it: 16-bit crops
+// reach them at twice the elements.  Every other size rule of the dispatch counts ELEMENTS (or the fp32 workspace's bytes).
 ForwardPlan plan_forward_gather(int num_rois, int channels, int NB, int nchunks, bool out_nhwc, bool launcher_rest, int groups = 1,
-                                size_t map_bytes_per_xcd = 0, bool allow_lines = true)
+                                size_t map_bytes_per_xcd = 0, bool allow_lines = true, size_t elem_bytes = sizeof(float))
 {
     const int base_dbg = (g_tune.fwd_dbg & ~0xe0) | (launcher_rest ? 32 : 0);   // bits 5-7 are the host's
     const int ntiles = ceil_div(NB, kTileBins);
@@ -483,7 +492,7 @@ ForwardPlan plan_forward_gather(int num_rois, int channels, int NB, int nchunks,
     // 251 / 176; 11 x 100, R = 600 (645 MB) 215 / 183.  Around the cache's size it is a draw or worse (267-275 MB: 80 / 87,
     // 73 / 87, 104 / 93, 76 / 83; 322-334 MB: 105 / 97, 112 / 108): from 320 MB up.
     if (allow_lines && NB % 16 != 0 && (g_tune.fwd_shift_lines == 2 ||
-                         (g_tune.fwd_shift_lines == 1 && (size_t)num_rois * channels * NB * sizeof(float) > ((size_t)320 << 20)))) {
+                         (g_tune.fwd_shift_lines == 1 && (size_t)num_rois * channels * NB * elem_bytes > ((size_t)320 << 20)))) {   // bytes
         const int nt = ceil_div(NB, kTileBins - 32);
         return {FwdKernel::kShiftLines, tiled_grid((long)num_rois * nt, nchunks, g_tune.shift_lines_wgs_per_cu), nt, base_dbg};
     }
@@ -496,7 +505,7 @@ ForwardPlan plan_forward_gather(int num_rois, int channels, int NB, int nchunks,
     // R = 128 15.7 / 15.6, R = 64 12.5 / 13.1, eight 160 x 160 maps (6.6 MB of map per XCD) 47.1 / 49.8 -- so: XCD groups, at
     // least 48 MB of crops, at most 2 MB of the chunk-major copy per XCD.
     if (g_tune.fwd_merge && groups > 1 && NB % 16 != 0 && (g_tune.fwd_merge > 1 ||
-        ((size_t)num_rois * channels * NB * sizeof(float) >= ((size_t)48 << 20) && map_bytes_per_xcd <= ((size_t)2 << 20))))
+        ((size_t)num_rois * channels * NB * elem_bytes >= ((size_t)48 << 20) && map_bytes_per_xcd <= ((size_t)2 << 20))))   // bytes
         return {FwdKernel::kStridedMerge, tiled_grid((long)num_rois * ntiles, nchunks, g_tune.split_wgs_per_cu), ntiles, base_dbg};
     if (NB % 4 != 0 || (g_tune.fwd_shift && (NB % 16 != 0 || g_tune.fwd_shift == 2))) {   // (rows of dwords: always)
         const int wpc = g_tune.shift_wgs_per_cu > 0 ? g_tune.shift_wgs_per_cu : kShiftWgsPerCu;
@@ -517,6 +526,9 @@ bool caller_ok(int caller, bool con_idx_allowed)
            (con_idx_allowed && caller == RROI_CALLER_LAUNCHER_CON_IDX);
 }
 
+inline bool dtype_ok(int dtype) { return dtype == RROI_DTYPE_FP32 || dtype == RROI_DTYPE_BF16 || dtype == RROI_DTYPE_FP16; }
+inline size_t dtype_bytes(int dtype) { return dtype == RROI_DTYPE_FP32 ? 4 : 2; }
+
 struct FwdDispatch {
     int status = 0;                  // 1: the call launches this plan; 0: it refuses its arguments
     int family = RROI_PLAN_NONE;
@@ -531,11 +543,17 @@ struct FwdDispatch {
     int cslab = 0;
 };
 
+// dtype (0.10.0): the element type of the map and the crops.  A 16-bit call is native-only, reads NCHW
+// features, and never takes the one-launch NCHW_SRC form; where an fp32 AUTO call would take it, a 16-bit call runs K2p.
 FwdDispatch plan_forward(int feature_layout, int top_layout, int batch_size, int num_rois, int height, int width,
-                         int channels, int pooled_height, int pooled_width, int path, int caller)
+                         int channels, int pooled_height, int pooled_width, int path, int caller, int dtype = RROI_DTYPE_FP32)
 {
     FwdDispatch P;
-    if (!caller_ok(caller, true)) return P;
+    if (!caller_ok(caller, true) || !dtype_ok(dtype)) return P;
+    const bool half = dtype != RROI_DTYPE_FP32;
+    if (half && (caller != RROI_CALLER_NATIVE || feature_layout != RROI_LAYOUT_NCHW ||
+                 (path & 0xff) == RROI_PATH_FUSED))
+        return P;
     if (path & ~(0xff | RROI_PATH_TRIG_FP32)) return P;   // unknown flag bits
     P.trig = (path & RROI_PATH_TRIG_FP32) ? RROI_TRIG_FP32 : RROI_TRIG_DOUBLE;
     path &= 0xff;
@@ -582,8 +600,12 @@ FwdDispatch plan_forward(int feature_layout, int top_layout, int batch_size, int
                 pick_tiled_fwd(batch_size, channels, height, width, num_rois, NB);
     else
         tiled = path == RROI_PATH_TILED;
-    // the one-launch form for few ROIs (the gather reading the NCHW map itself): NCHW in, NCHW out, not for the launcher
-    const bool fused = !P.launcher && !P.out_nhwc && feature_layout == RROI_LAYOUT_NCHW &&
+    // the one-launch form for few ROIs (the gather reading the NCHW map itself): NCHW in, NCHW out, not for the launcher,
+    // fp32 only.  A 16-bit call in its range stays on the direct path (K2p), which was never slower than the two-launch
+    // path there (tools/half_bench.py, profiles/half_precision.md; us per call, bf16 K2p / two-launch, back-to-back calls
+    // from Python): C = 256, 160 x 160, 8 x 64, R = 12 15.1 / 19.0, 16 15.0 / 18.7, 24 15.3 / 19.1, 28 15.5 / 19.2;
+    // C = 128, 11 x 50, R = 24 15.4 / 18.9, 32 14.7 / 18.6, 48 15.6 / 18.2 (fp32 AUTO, fused: 16.2 ... 34.2)
+    const bool fused = !half && !P.launcher && !P.out_nhwc && feature_layout == RROI_LAYOUT_NCHW &&
                        (path == RROI_PATH_FUSED ||
                         (path == RROI_PATH_AUTO && !tiled && pick_fused_fwd(batch_size, channels, height, width, num_rois, NB)));
     if (path == RROI_PATH_FUSED && !fused) return P;
@@ -612,7 +634,8 @@ FwdDispatch plan_forward(int feature_layout, int top_layout, int batch_size, int
     const size_t map_bytes_per_xcd =
         P.zero_copy ? (size_t)batch_size * height * width * channels * 4 / 8
                     : carve(nullptr, batch_size, channels, height, width, num_rois, feature_layout).cm_bytes / 8;
-    P.gather = plan_forward_gather(num_rois, channels, NB, P.nchunks, P.out_nhwc, P.launcher, P.groups, map_bytes_per_xcd);
+    P.gather = plan_forward_gather(num_rois, channels, NB, P.nchunks, P.out_nhwc, P.launcher, P.groups, map_bytes_per_xcd,
+                                   true, dtype_bytes(dtype));
     if ((long)num_rois * P.gather.ntiles >= (1L << 31)) return P;
     P.family = RROI_PLAN_FWD_TWO_LAUNCH;
     P.status = 1;
@@ -649,11 +672,18 @@ static inline bool gather_choice_is_open(int path)
     return path != RROI_PATH_TILED_LISTS && path != RROI_PATH_TILED_INKERNEL;
 }
 
+// dtype (0.10.0): the element type of top_diff and bottom_diff.  A 16-bit call is native-only, reads an
+// NCHW top_diff, and runs one of the three gathers (never the fp32-atomic DIRECT / ATOMIC forms): AUTO takes the gather
+// TILED would take, and a problem no gather can index is refused.
 BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch_size, int num_rois, int height, int width,
-                          int channels, int pooled_height, int pooled_width, int path, int caller)
+                          int channels, int pooled_height, int pooled_width, int path, int caller, int dtype = RROI_DTYPE_FP32)
 {
     BwdDispatch P;
-    if (!caller_ok(caller, false)) return P;
+    if (!caller_ok(caller, false) || !dtype_ok(dtype)) return P;
+    const bool half = dtype != RROI_DTYPE_FP32;
+    if (half && (caller != RROI_CALLER_NATIVE || top_diff_layout != RROI_LAYOUT_NCHW ||
+                 (path & 0xff) == RROI_PATH_DIRECT || (path & 0xff) == RROI_PATH_TILED_ATOMIC))
+        return P;
     if (path & ~(0xff | RROI_PATH_TRIG_FP32)) return P;   // unknown flag bits
     P.trig = (path & RROI_PATH_TRIG_FP32) ? RROI_TRIG_FP32 : RROI_TRIG_DOUBLE;
     path &= 0xff;
@@ -698,7 +728,7 @@ BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch
     const int NB = pooled_height * pooled_width;
     const size_t HW = (size_t)height * width;
     const bool accumulate = P.accumulate;
-    const bool tiled = td_nhwc || bd_nhwc || (path == RROI_PATH_AUTO
+    const bool tiled = half || td_nhwc || bd_nhwc || (path == RROI_PATH_AUTO
                                        ? pick_tiled_bwd(batch_size, channels, height, width, num_rois, NB)
                                        : path != RROI_PATH_DIRECT);
     if (accumulate && (!tiled || bd_nhwc)) return P;
@@ -715,6 +745,7 @@ BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch
     const BwdWorkspace ws = carve_bwd(nullptr, batch_size, channels, height, width, num_rois, NB);
     P.ws = ws;
     if ((td_nhwc || bd_nhwc) && (!ws.gather_ok || (size_t)num_rois * NB >= (1ull << 32))) return P;
+    if (half && !ws.gather_ok) return P;   // (the atomic scatter, an fp32 call's fallback, has no 16-bit form)
     const bool gather = path != RROI_PATH_TILED_ATOMIC && ws.gather_ok;
     // Two gathers.  K3t builds the pixel lists inside the gather kernel (rroi_backward_tile_kernels.h), K3g
     // with count / scan / fill launches in HBM.  Measured (tools/crossover.py, MI355X, us per call,
@@ -763,6 +794,9 @@ BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch
             P.relayout_blocks = blocks;
         }
         P.nk = nchunks > 4 ? 8 : nchunks > 2 ? 4 : nchunks > 1 ? 2 : 1;
+        // 16-bit calls: at most four chunks per lane (two passes beyond 128 channels) -- the eight-chunk instantiation
+        // spills to scratch (as the fp32 one does), and a 16-bit instantiation of it is not built
+        if (half && P.nk > 4) P.nk = 4;
         const unsigned ntiles = ws.keys.keys / 32u;
         const unsigned per_xcd = (ntiles + 7u) / 8u;
         P.grid = dim3(per_xcd * 8u);
@@ -1034,7 +1068,7 @@ ScratchLease launcher_scratch(hipStream_t stream, size_t bytes)
 // ====================================================================================
 extern "C" {
 
-const char* rroi_align_hip_version(void) { return "rroi_align_hip 0.9.0 gfx950"; }
+const char* rroi_align_hip_version(void) { return "rroi_align_hip 0.10.0 gfx950"; }
 
 size_t rroi_align_forward_workspace_bytes(int batch_size, int channels, int height, int width,
                                           int num_rois, int feature_layout)
@@ -1069,6 +1103,10 @@ static int forward_impl(const float* features, int feature_layout, int top_layou
                         int batch_size, int num_rois, int height, int width, int channels,
                         int pooled_height, int pooled_width, const float* rois, float* top_data,
                         void* workspace, size_t workspace_bytes, int path, int stages, void* stream_);
+static int forward_typed_impl(const void* features, int dtype, int feature_layout, int top_layout, float spatial_scale,
+                              int batch_size, int num_rois, int height, int width, int channels, int pooled_height,
+                              int pooled_width, const float* rois, void* top_data, void* workspace, size_t workspace_bytes,
+                              int path, int stages, void* stream_);
 
 int rroi_align_forward_stages_hip(const float* features, int feature_layout, float spatial_scale,
                                   int batch_size, int num_rois, int height, int width,
@@ -1095,11 +1133,16 @@ int rroi_align_forward_layout_hip(const float* features, int feature_layout, int
 // Launches the plan `P` (plan_forward on the same arguments).  The launcher's tiled plan (P.launcher): ROIs whose
 // image index is >= batch_size are sampled from the NCHW tensor by extra blocks of the prologue launch and left alone
 // by the gather; its direct kernels get no batch count (-1) and write con_idx where P.con_idx.
-static int launch_forward(const FwdDispatch& P, const float* features, int feature_layout, float spatial_scale,
+extern "C++" {   // (templates)
+// T: the element type of the map and the crops (float, bf16_t, fp16_t; the plan of a 16-bit call has no fused form, no
+// zero copy and no launcher)
+template <class T>
+static int launch_forward(const FwdDispatch& P, const T* features, int feature_layout, float spatial_scale,
                           int batch_size, int num_rois, int height, int width, int channels, int pooled_height,
-                          int pooled_width, const float* rois, float* top_data, float* idx_x, float* idx_y,
+                          int pooled_width, const float* rois, T* top_data, float* idx_x, float* idx_y,
                           void* workspace, size_t workspace_bytes, int stages, hipStream_t stream)
 {
+    constexpr bool kF32 = std::is_same<T, float>::value;
     const int NB = pooled_height * pooled_width;
     const int trig = P.trig;
     const int nchunks = P.nchunks;
@@ -1115,12 +1158,15 @@ static int launch_forward(const FwdDispatch& P, const float* features, int featu
         return launch_status();
     case RROI_PLAN_FWD_DIRECT_THREAD:
         if (!(stages & RROI_STAGE_GATHER)) return 1;
-        hipLaunchKernelGGL(rroi_fwd_direct_kernel, P.dgrid, dim3(256), 0, stream, features, rois, top_data,
+        hipLaunchKernelGGL(rroi_fwd_direct_kernel<T>, P.dgrid, dim3(256), 0, stream, features, rois, top_data,
                            P.con_idx ? idx_x : nullptr, P.con_idx ? idx_y : nullptr, num_rois, channels, height, width,
                            pooled_height, pooled_width, spatial_scale, trig, direct_batch, P.cslab);
         return launch_status();
     case RROI_PLAN_FWD_FUSED_STRIDED:
     case RROI_PLAN_FWD_FUSED_SHIFT: {
+        if constexpr (!kF32) {   // (fp32 only: no 16-bit plan)
+            return 0;
+        } else {
         if (!(stages & RROI_STAGE_GATHER)) return 1;  // one launch, run under the gather stage
         const ForwardPlan& plan = P.gather;
         const unsigned HWu = (unsigned)height * (unsigned)width;
@@ -1140,6 +1186,7 @@ static int launch_forward(const FwdDispatch& P, const float* features, int featu
         else RROI_FUSED(true, 0, 4, 3, false, 0, true);
 #undef RROI_FUSED
         return launch_status();
+        }
     }
     case RROI_PLAN_FWD_TWO_LAUNCH:
         break;
@@ -1151,7 +1198,8 @@ static int launch_forward(const FwdDispatch& P, const float* features, int featu
     if (!workspace || workspace_bytes < ws.bytes) return 0;
     const int HW = height * width;
     const bool zero_copy = P.zero_copy;
-    const float* map = zero_copy ? features : ws.cm;
+    const float* map = ws.cm;
+    if constexpr (kF32) map = zero_copy ? features : ws.cm;
     const int pitch = row_pitch(width);
     const int groups = P.groups;
     const bool launcher_rest = P.launcher;
@@ -1171,13 +1219,15 @@ static int launch_forward(const FwdDispatch& P, const float* features, int featu
         }
         const int aff_blocks = ceil_div(num_rois, 256);
         const int rest_blocks = launcher_rest ? num_rois : 0;
+        float* rest_out = nullptr;   // (the launcher: fp32)
+        if constexpr (kF32) rest_out = launcher_rest ? top_data : nullptr;
 #define RROI_LAUNCH_PRO(AUX)                                                                        \
-    hipLaunchKernelGGL(rroi_prologue_kernel<AUX>,                                                     \
+    hipLaunchKernelGGL((rroi_prologue_kernel<AUX, T>),                                                \
                        dim3(relayout_blocks + aff_blocks + (groups > 1 ? 1 : 0) + rest_blocks), dim3(256), 0, \
                        stream, features, ws.cm, channels, HW, width, pitch,                           \
                        make_fastdiv((unsigned)width), nchunks, ptiles, relayout_blocks,               \
                        relayout_tiles, batch_size, rois, num_rois, pooled_height,                     \
-                       spatial_scale, trig, ws.aff, aff_blocks, launcher_rest ? top_data : (float*)nullptr, \
+                       spatial_scale, trig, ws.aff, aff_blocks, rest_out,                             \
                        pooled_width, groups, ws.sort_rank, ws.sort_order)
         RROI_LAUNCH_PRO(0);   // plain stores: the copy stays in the L2s that wrote it (write-through: 1.8 us faster alone, the step is not)
 #undef RROI_LAUNCH_PRO
@@ -1202,37 +1252,64 @@ static int launch_forward(const FwdDispatch& P, const float* features, int featu
             lay.img_stride = lay.chunk_stride * (unsigned)nchunks;
         }
         const FastDiv dt = make_fastdiv((unsigned)ntiles), dp = make_fastdiv((unsigned)pooled_width);
-        // the shipped instantiations of rroi_fwd_split_kernel<VEC_STORE, EARLY, OCC, HID, ONHWC, SHIFT>, one per FwdKernel
+        // the shipped instantiations of rroi_fwd_split_kernel<VEC_STORE, EARLY, OCC, HID, ONHWC, SHIFT, NCHW_SRC, WAUX, T>,
+        // one per FwdKernel and element type
 #define RROI_GATHER(...)                                                                                              \
     hipLaunchKernelGGL((rroi_fwd_split_kernel<__VA_ARGS__>), dim3(plan.grid), dim3(2 * kWave), 0, stream, map, ws.aff, \
                        top_data, num_rois, channels, height, width, pooled_width, NB, batch_size, nchunks, ntiles, lay, \
                        dt, dp, plan.dbg, XcdGroups{groups, ws.sort_order})
         switch (plan.kernel) {
-        case FwdKernel::kStrided:       RROI_GATHER(true, 0, 6, 3, false, 0); break;   // 62-64 VGPRs, 12.1 KB of LDS: 12 per CU
-        case FwdKernel::kChannelsLast:  RROI_GATHER(true, 2, 5, 2, true, 0); break;    // 91 VGPRs: 10 per CU
-        case FwdKernel::kShift:         RROI_GATHER(true, 0, 6, 3, false, 1); break;    // 79 VGPRs, 12.4 KB of LDS: 12 per CU
-        case FwdKernel::kStridedMerge:  RROI_GATHER(true, 0, 6, 3, false, 0, false, 0); break;   // plain stores (write-through: 32.1 against 30.1 us)
-        case FwdKernel::kShiftLines:    RROI_GATHER(true, 0, 5, 3, false, 2); break;    // 84 VGPRs, 14.8 KB of LDS: 10 per CU
+        case FwdKernel::kStrided:       RROI_GATHER(true, 0, 6, 3, false, 0, false, -1, T); break;   // 62-64 VGPRs, 12.1 KB of LDS: 12 per CU
+        case FwdKernel::kChannelsLast:  RROI_GATHER(true, 2, 5, 2, true, 0, false, -1, T); break;    // 91 VGPRs: 10 per CU
+        case FwdKernel::kShift:         RROI_GATHER(true, 0, 6, 3, false, 1, false, -1, T); break;   // 79 VGPRs, 12.4 KB of LDS: 12 per CU
+        case FwdKernel::kStridedMerge:  RROI_GATHER(true, 0, 6, 3, false, 0, false, 0, T); break;    // plain stores (write-through: 32.1 against 30.1 us)
+        case FwdKernel::kShiftLines:    RROI_GATHER(true, 0, 5, 3, false, 2, false, -1, T); break;   // 84 VGPRs, 14.8 KB of LDS: 10 per CU
         }
 #undef RROI_GATHER
     }
     return launch_status();
 }
+}  // extern "C++"
 
 static int forward_impl(const float* features, int feature_layout, int top_layout, float spatial_scale,
                         int batch_size, int num_rois, int height, int width, int channels,
                         int pooled_height, int pooled_width, const float* rois, float* top_data,
                         void* workspace, size_t workspace_bytes, int path, int stages, void* stream_)
 {
+    return forward_typed_impl(features, RROI_DTYPE_FP32, feature_layout, top_layout, spatial_scale, batch_size, num_rois,
+                              height, width, channels, pooled_height, pooled_width, rois, top_data, workspace,
+                              workspace_bytes, path, stages, stream_);
+}
+
+static int forward_typed_impl(const void* features, int dtype, int feature_layout, int top_layout, float spatial_scale,
+                              int batch_size, int num_rois, int height, int width, int channels, int pooled_height,
+                              int pooled_width, const float* rois, void* top_data, void* workspace, size_t workspace_bytes,
+                              int path, int stages, void* stream_)
+{
     if ((stages & ~RROI_STAGE_ALL) || stages == 0) return 0;
     const FwdDispatch P = plan_forward(feature_layout, top_layout, batch_size, num_rois, height, width, channels,
-                                       pooled_height, pooled_width, path, RROI_CALLER_NATIVE);
+                                       pooled_height, pooled_width, path, RROI_CALLER_NATIVE, dtype);
     if (!P.status) return 0;
     if (P.family == RROI_PLAN_NONE) return 1;
     if (!features || !rois || !top_data) return 0;
-    return launch_forward(P, features, feature_layout, spatial_scale, batch_size, num_rois, height, width, channels,
-                          pooled_height, pooled_width, rois, top_data, nullptr, nullptr, workspace, workspace_bytes,
-                          stages, static_cast<hipStream_t>(stream_));
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    auto run = [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_forward(P, static_cast<const T*>(features), feature_layout, spatial_scale, batch_size, num_rois,
+                              height, width, channels, pooled_height, pooled_width, rois, static_cast<T*>(top_data),
+                              nullptr, nullptr, workspace, workspace_bytes, stages, stream);
+    };
+    return dtype == RROI_DTYPE_BF16 ? run(bf16_t{}) : dtype == RROI_DTYPE_FP16 ? run(fp16_t{}) : run(float{});
+}
+
+int rroi_align_forward_typed_hip(const void* features, int dtype, int feature_layout, int top_layout, float spatial_scale,
+                                 int batch_size, int num_rois, int height, int width, int channels, int pooled_height,
+                                 int pooled_width, const float* rois, void* top_data, void* workspace,
+                                 size_t workspace_bytes, int path, void* stream_)
+{
+    return forward_typed_impl(features, dtype, feature_layout, top_layout, spatial_scale, batch_size, num_rois, height,
+                              width, channels, pooled_height, pooled_width, rois, top_data, workspace, workspace_bytes,
+                              path, RROI_STAGE_ALL, stream_);
 }
 
 int rroi_align_backward_hip(const float* top_diff, float spatial_scale, int batch_size,
@@ -1251,6 +1328,20 @@ static int backward_impl(const float* top_diff, int top_diff_layout, int bottom_
                          float spatial_scale, int batch_size, int num_rois, int height, int width, int channels,
                          int pooled_height, int pooled_width, const float* rois, float* bottom_diff,
                          void* workspace, size_t workspace_bytes, int path, void* stream_);
+static int backward_typed_impl(const void* top_diff, int dtype, int top_diff_layout, int bottom_diff_layout,
+                               float spatial_scale, int batch_size, int num_rois, int height, int width, int channels,
+                               int pooled_height, int pooled_width, const float* rois, void* bottom_diff,
+                               void* workspace, size_t workspace_bytes, int path, void* stream_);
+
+int rroi_align_backward_typed_hip(const void* top_diff, int dtype, int top_diff_layout, int bottom_diff_layout,
+                                  float spatial_scale, int batch_size, int num_rois, int height, int width, int channels,
+                                  int pooled_height, int pooled_width, const float* rois, void* bottom_diff,
+                                  void* workspace, size_t workspace_bytes, int path, void* stream_)
+{
+    return backward_typed_impl(top_diff, dtype, top_diff_layout, bottom_diff_layout, spatial_scale, batch_size, num_rois,
+                               height, width, channels, pooled_height, pooled_width, rois, bottom_diff, workspace,
+                               workspace_bytes, path, stream_);
+}
 
 int rroi_align_backward_layout_hip(const float* top_diff, int top_diff_layout, int bottom_diff_layout,
                                    float spatial_scale, int batch_size, int num_rois, int height,
@@ -1264,25 +1355,33 @@ int rroi_align_backward_layout_hip(const float* top_diff, int top_diff_layout, i
 }
 
 // Launches the plan `P` (plan_backward on the same arguments); P.accumulate: bottom_diff += gradient.
-static int launch_backward(const BwdDispatch& P, const float* top_diff, float spatial_scale, int batch_size, int num_rois,
+extern "C++" {   // (templates)
+// T: the element type of top_diff and bottom_diff (the plan of a 16-bit call is a gather, NCHW top_diff, not accumulating)
+template <class T>
+static int launch_backward(const BwdDispatch& P, const T* top_diff, float spatial_scale, int batch_size, int num_rois,
                            int height, int width, int channels, int pooled_height, int pooled_width, const float* rois,
-                           float* bottom_diff, void* workspace, size_t workspace_bytes, hipStream_t stream)
+                           T* bottom_diff, void* workspace, size_t workspace_bytes, hipStream_t stream)
 {
+    constexpr bool kF32 = std::is_same<T, float>::value;
     const int trig = P.trig;
     const int NB = pooled_height * pooled_width;
     const size_t HW = (size_t)height * width;
-    const size_t in_bytes = (size_t)batch_size * channels * HW * sizeof(float);
-    const bool td_nhwc = P.td_nhwc, bd_nhwc = P.bd_nhwc, accumulate = P.accumulate;
+    const size_t in_bytes = (size_t)batch_size * channels * HW * sizeof(T);
+    const bool td_nhwc = P.td_nhwc, accumulate = P.accumulate;
     switch (P.family) {
     case RROI_PLAN_NONE:
         return accumulate ? 1 : status_of(hipMemsetAsync(bottom_diff, 0, in_bytes, stream));
     case RROI_PLAN_BWD_DIRECT: {
-        hipError_t e = hipMemsetAsync(bottom_diff, 0, in_bytes, stream);
-        if (e != hipSuccess) return status_of(e);
-        hipLaunchKernelGGL(rroi_bwd_direct_kernel, P.grid, dim3(256), 0, stream, top_diff, rois,
-                           bottom_diff, num_rois, channels, height, width, pooled_height,
-                           pooled_width, spatial_scale, trig, batch_size, P.cslab);
-        return launch_status();
+        if constexpr (!kF32) {   // (fp32 atomics: no 16-bit plan)
+            return 0;
+        } else {
+            hipError_t e = hipMemsetAsync(bottom_diff, 0, in_bytes, stream);
+            if (e != hipSuccess) return status_of(e);
+            hipLaunchKernelGGL(rroi_bwd_direct_kernel, P.grid, dim3(256), 0, stream, top_diff, rois,
+                               bottom_diff, num_rois, channels, height, width, pooled_height,
+                               pooled_width, spatial_scale, trig, batch_size, P.cslab);
+            return launch_status();
+        }
     }
     case RROI_PLAN_BWD_ATOMIC:
     case RROI_PLAN_BWD_INKERNEL:
@@ -1295,6 +1394,10 @@ static int launch_backward(const BwdDispatch& P, const float* top_diff, float sp
 
     const BwdWorkspace ws = carve_bwd(workspace, batch_size, channels, height, width, num_rois, NB);
     if (!workspace || workspace_bytes < ws.bytes) return 0;
+    if (!kF32 && (P.family == RROI_PLAN_BWD_ATOMIC || td_nhwc || accumulate)) return 0;
+    // where the gather reads top_diff: the relaid-out fp32 copy, or an fp32 channels-last top_diff in place
+    const float* srcT = ws.tdT;
+    if constexpr (kF32) srcT = td_nhwc ? top_diff : ws.tdT;
     const int nchunks = P.nchunks;
     const int pitch = row_pitch(width);
     const int ptiles = ceil_div((long)HW, kRelayoutPx);
@@ -1330,7 +1433,7 @@ static int launch_backward(const BwdDispatch& P, const float* top_diff, float sp
             const long tiles = P.tiles;
             const long blocks = P.relayout_blocks;
 #define RROI_LAUNCH_R(SAUX)                                                                              \
-    hipLaunchKernelGGL((rroi_bwd_pairs_relayout_kernel<0, SAUX>), dim3((unsigned)blocks), dim3(256), 0,       \
+    hipLaunchKernelGGL((rroi_bwd_pairs_relayout_kernel<0, SAUX, T>), dim3((unsigned)blocks), dim3(256), 0,       \
                        stream, ws.aff, num_rois, height, width, pooled_width, NB, batch_size, lines_per_roi, \
                        dnb, dpw, KL, ws.cnt, ws.off, ws.bsum, ws.pairs, 0, top_diff, ws.tdT, channels,       \
                        nchunks, tt, (int)blocks, 0, (int)tiles, ws.scan_blocks, 0,                          \
@@ -1343,17 +1446,23 @@ static int launch_backward(const BwdDispatch& P, const float* top_diff, float sp
         const unsigned ntiles = KL.keys / 32u;
         const unsigned per_xcd = P.grid.x / 8u;
         const FastDiv dbt = make_fastdiv(KL.Ht * KL.Wt), dwt = make_fastdiv(KL.Wt), dph = make_fastdiv((unsigned)pooled_height);
-        float* dst = bd_nhwc ? bottom_diff : ws.gcm;
-        const float* srcT = td_nhwc ? top_diff : ws.tdT;
+        // NHWC: the caller's bottom_diff in place (its type); else the fp32 chunk-major scratch
 #define RROI_LAUNCH_TG(NK, NHWC)                                                                          \
-    hipLaunchKernelGGL((rroi_bwd_tile_gather_kernel<NK, NHWC>), P.grid, dim3(kTgThreads), 0, stream,         \
-                       srcT, ws.aff, dst, num_rois, channels, height, width, pitch, pooled_height,           \
+    hipLaunchKernelGGL((rroi_bwd_tile_gather_kernel<NK, NHWC, std::conditional_t<NHWC, T, float>>), P.grid,  \
+                       dim3(kTgThreads), 0, stream,                                                          \
+                       srcT, ws.aff, NHWC ? (std::conditional_t<NHWC, T, float>*)(void*)bottom_diff          \
+                                          : (std::conditional_t<NHWC, T, float>*)(void*)ws.gcm,              \
+                       num_rois, channels, height, width, pitch, pooled_height,                              \
                        pooled_width, batch_size, nchunks, chunk_stride, line_stride, lines_per_roi, KL,      \
                        ntiles, per_xcd, dbt, dwt, dph)
 #define RROI_LAUNCH_TG_NK(NHWC)                          \
     do {                                                 \
-        if (P.nk == 8) RROI_LAUNCH_TG(8, NHWC);          \
-        else if (P.nk == 4) RROI_LAUNCH_TG(4, NHWC);     \
+        if constexpr (kF32)   /* (16-bit: nk <= 4) */    \
+            if (P.nk == 8) {                             \
+                RROI_LAUNCH_TG(8, NHWC);                 \
+                break;                                   \
+            }                                            \
+        if (P.nk == 4) RROI_LAUNCH_TG(4, NHWC);          \
         else if (P.nk == 2) RROI_LAUNCH_TG(2, NHWC);     \
         else RROI_LAUNCH_TG(1, NHWC);                    \
     } while (0)
@@ -1388,7 +1497,7 @@ static int launch_backward(const BwdDispatch& P, const float* top_diff, float sp
             return n / unit <= cap ? n / unit : cap;
         };
 #define RROI_LAUNCH_PR(FILL, SAUX, BLOCKS, T0, T1)                                                   \
-    hipLaunchKernelGGL((rroi_bwd_pairs_relayout_kernel<FILL, SAUX>), dim3((unsigned)(pblocks + (BLOCKS))), \
+    hipLaunchKernelGGL((rroi_bwd_pairs_relayout_kernel<FILL, SAUX, T>), dim3((unsigned)(pblocks + (BLOCKS))), \
                        dim3(256), 0, stream, ws.aff, num_rois, height, width, pooled_width, NB,          \
                        batch_size, lines_per_roi, dnb, dpw, KL, ws.cnt, ws.off, ws.bsum, ws.pairs,       \
                        pblocks, top_diff, ws.tdT, channels, nchunks, tt, (int)(BLOCKS), (int)(T0), (int)(T1),            \
@@ -1418,8 +1527,9 @@ static int launch_backward(const BwdDispatch& P, const float* top_diff, float sp
         // the lists: count / scan / fill segments (`off` = scanned offsets) or buckets (`off` = the counters)
         const unsigned* loff = buckets ? reinterpret_cast<const unsigned*>(ws.cnt) : ws.off;
 #define RROI_LAUNCH_G(DSTK, BUCK, DST)                                                                        \
-    hipLaunchKernelGGL((rroi_bwd_gather_kernel<DSTK, BUCK>), P.grid, dim3(256), 0, stream,                    \
-                       td_nhwc ? top_diff : ws.tdT, loff, ws.bsum, ws.pairs, DST, channels, height, width,    \
+    hipLaunchKernelGGL((rroi_bwd_gather_kernel<DSTK, BUCK, std::remove_pointer_t<decltype(DST)>>), P.grid,    \
+                       dim3(256), 0, stream,                                                                  \
+                       srcT, loff, ws.bsum, ws.pairs, DST, channels, height, width,                           \
                        pitch, nchunks, chunk_stride, line_stride, sub_shift, KL, make_fastdiv(KL.Ht * KL.Wt), \
                        make_fastdiv(KL.Wt), ws.scan_blocks, raw_bsum, BL, tile_run)
         switch (P.dest) {
@@ -1428,8 +1538,10 @@ static int launch_backward(const BwdDispatch& P, const float* top_diff, float sp
             else RROI_LAUNCH_G(kDstNhwc, false, bottom_diff);
             return launch_status();
         case RROI_PLAN_DST_NCHW_ADD:
-            if (buckets) RROI_LAUNCH_G(kDstNchwAdd, true, bottom_diff);
-            else RROI_LAUNCH_G(kDstNchwAdd, false, bottom_diff);
+            if constexpr (kF32) {   // (the launcher)
+                if (buckets) RROI_LAUNCH_G(kDstNchwAdd, true, bottom_diff);
+                else RROI_LAUNCH_G(kDstNchwAdd, false, bottom_diff);
+            }
             return launch_status();
         case RROI_PLAN_DST_NCHW:
             if (buckets) RROI_LAUNCH_G(kDstNchw, true, bottom_diff);
@@ -1443,7 +1555,7 @@ static int launch_backward(const BwdDispatch& P, const float* top_diff, float sp
 #undef RROI_LAUNCH_G
         st = launch_status();
         if (st != 1) return st;
-    } else {
+    } else if constexpr (kF32) {
         hipError_t e = hipMemsetAsync(ws.gcm, 0, (size_t)batch_size * nchunks * height * pitch * kLineBytes, stream);
         if (e != hipSuccess) return status_of(e);
         const int ntiles = P.ntiles;
@@ -1459,15 +1571,37 @@ static int launch_backward(const BwdDispatch& P, const float* top_diff, float sp
         st = launch_status();
         if (st != 1) return st;
     }
-    if (accumulate)
-        hipLaunchKernelGGL(rroi_cm_to_nchw_kernel<true>, dim3(ptiles * nchunks * batch_size), dim3(256), 0,
-                           stream, ws.gcm, bottom_diff, channels, (int)HW, width, pitch,
-                           make_fastdiv((unsigned)width), nchunks, ptiles);
-    else
-        hipLaunchKernelGGL(rroi_cm_to_nchw_kernel<false>, dim3(ptiles * nchunks * batch_size), dim3(256), 0,
+    if (accumulate) {
+        if constexpr (kF32)
+            hipLaunchKernelGGL(rroi_cm_to_nchw_kernel<true>, dim3(ptiles * nchunks * batch_size), dim3(256), 0,
+                               stream, ws.gcm, bottom_diff, channels, (int)HW, width, pitch,
+                               make_fastdiv((unsigned)width), nchunks, ptiles);
+    } else
+        hipLaunchKernelGGL((rroi_cm_to_nchw_kernel<false, T>), dim3(ptiles * nchunks * batch_size), dim3(256), 0,
                            stream, ws.gcm, bottom_diff, channels, (int)HW, width, pitch,
                            make_fastdiv((unsigned)width), nchunks, ptiles);
     return launch_status();
+}
+}  // extern "C++"
+
+static int backward_typed_impl(const void* top_diff, int dtype, int top_diff_layout, int bottom_diff_layout,
+                               float spatial_scale, int batch_size, int num_rois, int height, int width, int channels,
+                               int pooled_height, int pooled_width, const float* rois, void* bottom_diff,
+                               void* workspace, size_t workspace_bytes, int path, void* stream_)
+{
+    const BwdDispatch P = plan_backward(top_diff_layout, bottom_diff_layout, batch_size, num_rois, height, width, channels,
+                                        pooled_height, pooled_width, path, RROI_CALLER_NATIVE, dtype);
+    if (!P.status) return 0;
+    if (!bottom_diff) return 0;
+    if (P.family != RROI_PLAN_NONE && (!top_diff || !rois)) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    auto run = [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_backward(P, static_cast<const T*>(top_diff), spatial_scale, batch_size, num_rois, height, width,
+                               channels, pooled_height, pooled_width, rois, static_cast<T*>(bottom_diff), workspace,
+                               workspace_bytes, stream);
+    };
+    return dtype == RROI_DTYPE_BF16 ? run(bf16_t{}) : dtype == RROI_DTYPE_FP16 ? run(fp16_t{}) : run(float{});
 }
 
 static int backward_impl(const float* top_diff, int top_diff_layout, int bottom_diff_layout,
@@ -1475,13 +1609,9 @@ static int backward_impl(const float* top_diff, int top_diff_layout, int bottom_
                          int pooled_height, int pooled_width, const float* rois, float* bottom_diff,
                          void* workspace, size_t workspace_bytes, int path, void* stream_)
 {
-    const BwdDispatch P = plan_backward(top_diff_layout, bottom_diff_layout, batch_size, num_rois, height, width, channels,
-                                        pooled_height, pooled_width, path, RROI_CALLER_NATIVE);
-    if (!P.status) return 0;
-    if (!bottom_diff) return 0;
-    if (P.family != RROI_PLAN_NONE && (!top_diff || !rois)) return 0;
-    return launch_backward(P, top_diff, spatial_scale, batch_size, num_rois, height, width, channels, pooled_height,
-                           pooled_width, rois, bottom_diff, workspace, workspace_bytes, static_cast<hipStream_t>(stream_));
+    return backward_typed_impl(top_diff, RROI_DTYPE_FP32, top_diff_layout, bottom_diff_layout, spatial_scale, batch_size,
+                               num_rois, height, width, channels, pooled_height, pooled_width, rois, bottom_diff,
+                               workspace, workspace_bytes, path, stream_);
 }
 
 int rroi_align_bin_centres_hip(float spatial_scale, int num_rois, int height, int width,
@@ -1714,9 +1844,17 @@ int rroi_align_forward_plan(int feature_layout, int top_layout, int batch_size, 
                             int channels, int pooled_height, int pooled_width, int path, int caller,
                             rroi_align_plan* plan)
 {
+    return rroi_align_forward_plan_typed(RROI_DTYPE_FP32, feature_layout, top_layout, batch_size, num_rois, height, width,
+                                         channels, pooled_height, pooled_width, path, caller, plan);
+}
+
+int rroi_align_forward_plan_typed(int dtype, int feature_layout, int top_layout, int batch_size, int num_rois, int height,
+                                  int width, int channels, int pooled_height, int pooled_width, int path, int caller,
+                                  rroi_align_plan* plan)
+{
     if (!plan) return 0;
     const FwdDispatch P = plan_forward(feature_layout, top_layout, batch_size, num_rois, height, width, channels,
-                                       pooled_height, pooled_width, path, caller);
+                                       pooled_height, pooled_width, path, caller, dtype);
     if (!P.status) return 0;
     const bool gathers = P.family == RROI_PLAN_FWD_FUSED_STRIDED || P.family == RROI_PLAN_FWD_FUSED_SHIFT ||
                          P.family == RROI_PLAN_FWD_TWO_LAUNCH;
@@ -1733,9 +1871,17 @@ int rroi_align_backward_plan(int top_diff_layout, int bottom_diff_layout, int ba
                              int width, int channels, int pooled_height, int pooled_width, int path, int caller,
                              rroi_align_plan* plan)
 {
+    return rroi_align_backward_plan_typed(RROI_DTYPE_FP32, top_diff_layout, bottom_diff_layout, batch_size, num_rois, height,
+                                          width, channels, pooled_height, pooled_width, path, caller, plan);
+}
+
+int rroi_align_backward_plan_typed(int dtype, int top_diff_layout, int bottom_diff_layout, int batch_size, int num_rois,
+                                   int height, int width, int channels, int pooled_height, int pooled_width, int path,
+                                   int caller, rroi_align_plan* plan)
+{
     if (!plan) return 0;
     const BwdDispatch P = plan_backward(top_diff_layout, bottom_diff_layout, batch_size, num_rois, height, width, channels,
-                                        pooled_height, pooled_width, path, caller);
+                                        pooled_height, pooled_width, path, caller, dtype);
     if (!P.status) return 0;
     const bool lists = P.family == RROI_PLAN_BWD_LISTS || P.family == RROI_PLAN_BWD_BUCKETS;
     fill_plan(plan, P.family, -1, 0, P.family == RROI_PLAN_BWD_ATOMIC ? P.ntiles : 0,

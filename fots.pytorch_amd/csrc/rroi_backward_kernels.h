@@ -262,12 +262,13 @@ __device__ __forceinline__ void pairs_body(unsigned idx, const Affine* __restric
 // the pair lists -- bound by the atomic request rate -- and the rest relay out tiles
 // [tile_begin, tile_end) of top_diff -- bound by HBM.  They share the chip instead of running
 // one after the other; the host gives each of the two launches half of the tiles.
-template <int MODE, int SAUX>
+// TS: the element type of the caller's top_diff (the copy is fp32)
+template <int MODE, int SAUX, class TS = float>
 __global__ __launch_bounds__(256, 7) void rroi_bwd_pairs_relayout_kernel(   // (seven workgroups per CU: <= 72 VGPRs, as in rounds 3-4)
     const Affine* __restrict__ aff, int num_rois, int height, int width, int pooled_width, int NB,
     int batch_size, unsigned lines_per_roi, PatchMap pm, FastDiv div_pw, KeyLayout L,
     int* __restrict__ cnt, const unsigned* __restrict__ off, const unsigned* __restrict__ bsum,
-    uint2* __restrict__ pairs, int pair_blocks, const float* __restrict__ top_diff,
+    uint2* __restrict__ pairs, int pair_blocks, const TS* __restrict__ top_diff,
     float* __restrict__ tdT, int C, int nchunks, int ptiles, int relayout_blocks, int tile_begin,
     int tile_end, unsigned scan_blocks, int raw_bsum, BucketLists bl = BucketLists{0u, nullptr, nullptr, nullptr},
     int skip_dead_bins = 1)   // flags: bit 0 dead bins are not copied, bit 1 the pair blocks aggregate their reservations per wave
@@ -370,10 +371,12 @@ __global__ __launch_bounds__(1024) void rroi_scan2_kernel(unsigned* __restrict__
 // channel: the chunk-major round trip (26 MB written, read, written again at cfg3) and its launch are gone.  The
 // host deals the channel passes to blockIdx.y then (a pass = sub / 8 chunks), so that a pixel still takes one round.
 enum GatherDst { kDstChunkMajor = 0, kDstNhwc = 1, kDstNchw = 2, kDstNchwAdd = 3 };
-template <int DST, bool BUCKET = false>
+// TO: the element type of the destination -- the caller's bottom_diff (kDstNhwc, kDstNchw: sums in fp32, rounded once
+// where they are stored) or the fp32 scratch (kDstChunkMajor)
+template <int DST, bool BUCKET = false, class TO = float>
 __global__ __launch_bounds__(256) void rroi_bwd_gather_kernel(
     const float* __restrict__ tdT, const unsigned* __restrict__ off, const unsigned* __restrict__ bsum,
-    const uint2* __restrict__ pairs, float* __restrict__ gcm, int C, int height, int width, int pitch,
+    const uint2* __restrict__ pairs, TO* __restrict__ gcm, int C, int height, int width, int pitch,
     int nchunks, unsigned chunk_stride, unsigned line_stride, unsigned sub_shift, KeyLayout L,
     FastDiv div_bt, FastDiv div_wt, unsigned scan_blocks, int raw_bsum,
     BucketLists bl = BucketLists{0u, nullptr, nullptr, nullptr}, unsigned tile_run = 0u)
@@ -529,26 +532,26 @@ __global__ __launch_bounds__(256) void rroi_bwd_gather_kernel(
             const unsigned y0 = by0 * 4u + (in0 >> 3), x0 = (r0 - by0 * L.Wt) * 8u + (in0 & 7u);
             const unsigned cg = k0 * kChunk + c;
             if (key0 < L.keys && cg < (unsigned)C && y0 < (unsigned)height && x0 < (unsigned)width) {
-                float* o = gcm + (((size_t)b0 * C + cg) * height + y0) * (size_t)width + x0;
-                if ((width & 3) == 0 && (reinterpret_cast<uintptr_t>(gcm) & 15) == 0) {
-                    v4f* o4 = reinterpret_cast<v4f*>(o);   // x0 % 4 == 0 and W % 4 == 0: inside together
-                    if (DST == kDstNchwAdd) v += *o4;
-                    *o4 = v;
+                TO* o = gcm + (((size_t)b0 * C + cg) * height + y0) * (size_t)width + x0;
+                if ((width & 3) == 0 && (reinterpret_cast<uintptr_t>(gcm) & (4 * sizeof(TO) - 1)) == 0) {
+                    // x0 % 4 == 0 and W % 4 == 0: inside together
+                    if (DST == kDstNchwAdd) v += load4(o);
+                    store4(o, v);
                 } else {
                     const float e[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        if (x0 + j < (unsigned)width) o[j] = DST == kDstNchwAdd ? o[j] + e[j] : e[j];
+                        if (x0 + j < (unsigned)width) o[j] = from_f32<TO>(DST == kDstNchwAdd ? to_f32(o[j]) + e[j] : e[j]);
                 }
             }
             if (k0 + kstep < (unsigned)nchunks) __syncthreads();   // the next pass reuses the tile
         } else if (c_ok) {
             // chunk-major gradient (relaid out to NCHW afterwards), or the caller's channels-last
             // gradient (B, H, W, C) written directly: `gcm` is then bottom_diff itself
-            float* dst = DST_NHWC
-                             ? gcm + (((size_t)b * height + y) * width + x) * (size_t)C + k * kChunk + quad * 4u
-                             : gcm + (((size_t)b * nchunks + k) * slice_px + (size_t)y * pitch + x) * kChunk + quad * 4u;
-            *reinterpret_cast<v4f*>(dst) = acc;
+            TO* dst = DST_NHWC
+                          ? gcm + (((size_t)b * height + y) * width + x) * (size_t)C + k * kChunk + quad * 4u
+                          : gcm + (((size_t)b * nchunks + k) * slice_px + (size_t)y * pitch + x) * kChunk + quad * 4u;
+            store4(dst, acc);
         }
     }
 }
@@ -663,9 +666,10 @@ __global__ __launch_bounds__(kWave) void rroi_bwd_tiled_kernel(
 // chunk-major gradient (B, nchunks, HW, 32) -> NCHW (B, C, HW); inverse of the prologue's tile.
 // ACCUM (the reference-ABI launcher): bottom_diff += the gradient, as the reference's atomicAdds onto its
 // zeroed buffer do (kernel.cu:260-274) -- a caller that accumulates over several calls gets the sum
-template <bool ACCUM = false>
+// TO: the element type of the caller's bottom_diff (rounded once, here)
+template <bool ACCUM = false, class TO = float>
 __global__ __launch_bounds__(256) void rroi_cm_to_nchw_kernel(const float* __restrict__ cm,
-                                                              float* __restrict__ nchw, int C,
+                                                              TO* __restrict__ nchw, int C,
                                                               int HW, int width, int pitch,
                                                               FastDiv div_w, int nchunks, int ptiles)
 {
@@ -695,10 +699,10 @@ __global__ __launch_bounds__(256) void rroi_cm_to_nchw_kernel(const float* __res
         tw[3 * (kRelayoutPx + 1)] = v.w;
     }
     __syncthreads();
-    float* dst = nchw + ((size_t)b * C + c0) * HW + p0;
+    TO* dst = nchw + ((size_t)b * C + c0) * HW + p0;
     // rows of 16-byte aligned float4 (p0 is a multiple of 128): four 16-byte stores per thread instead of sixteen
     // dwords -- a wave instruction writes two 512-byte runs (the prologue's read mapping, mirrored)
-    if ((HW & 3) == 0 && (reinterpret_cast<uintptr_t>(nchw) & 15) == 0) {
+    if ((HW & 3) == 0 && (reinterpret_cast<uintptr_t>(nchw) & (4 * sizeof(TO) - 1)) == 0) {
         const int x4 = lane & 31, csub = lane >> 5;
         const int p = 4 * x4;
 #pragma unroll
@@ -707,9 +711,9 @@ __global__ __launch_bounds__(256) void rroi_cm_to_nchw_kernel(const float* __res
             if (c0 + c < C && p0 + p < HW) {   // HW % 4 == 0: the four pixels are inside together
                 const float* tr = T + c * (kRelayoutPx + 1) + p;
                 v4f v = {tr[0], tr[1], tr[2], tr[3]};
-                v4f* o = reinterpret_cast<v4f*>(dst + (size_t)c * HW + p);
-                if (ACCUM) v += *o;
-                *o = v;
+                TO* o = dst + (size_t)c * HW + p;
+                if (ACCUM) v += load4(o);
+                store4(o, v);
             }
         }
         return;
@@ -721,9 +725,9 @@ __global__ __launch_bounds__(256) void rroi_cm_to_nchw_kernel(const float* __res
         for (int hlf = 0; hlf < 2; ++hlf) {
             const int p = hlf * 64 + lane;
             if (c0 + c < C && p0 + p < HW) {
-                float* o = dst + (size_t)c * HW + p;
+                TO* o = dst + (size_t)c * HW + p;
                 const float v = T[c * (kRelayoutPx + 1) + p];
-                *o = ACCUM ? *o + v : v;
+                *o = from_f32<TO>(ACCUM ? to_f32(*o) + v : v);
             }
         }
     }

@@ -125,9 +125,11 @@ __device__ __forceinline__ void tg_accumulate(v4f (&acc)[NK], const bool (&cok)[
 }
 
 // NK = channel chunks a lane accumulates per pass (1, 2, 4, 8): a pass covers NK * 32 channels
-template <int NK, bool DST_NHWC>
+// TO: the element type of the destination -- the caller's channels-last bottom_diff (DST_NHWC: sums in fp32, rounded
+// once where they are stored) or the fp32 chunk-major scratch
+template <int NK, bool DST_NHWC, class TO = float>
 __global__ __launch_bounds__(kTgThreads, 4) void rroi_bwd_tile_gather_kernel(
-    const float* __restrict__ tdT, const Affine* __restrict__ aff, float* __restrict__ gcm, int num_rois, int C,
+    const float* __restrict__ tdT, const Affine* __restrict__ aff, TO* __restrict__ gcm, int num_rois, int C,
     int height, int width, int pitch, int pooled_height, int pooled_width, int batch_size, int nchunks,
     unsigned chunk_stride, unsigned line_stride, unsigned lines_per_roi, KeyLayout L, unsigned ntiles,
     unsigned per_xcd, FastDiv div_bt, FastDiv div_wt, FastDiv div_ph)
@@ -349,10 +351,10 @@ __global__ __launch_bounds__(kTgThreads, 4) void rroi_bwd_tile_gather_kernel(
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
                 if (!cok[k]) continue;
-                float* dst = DST_NHWC
-                                 ? gcm + (((size_t)bimg * height + y) * width + x) * (size_t)C + (k0 + k) * kChunk + q * 4u
-                                 : gcm + (((size_t)bimg * nchunks + (k0 + k)) * slice_px + (size_t)y * pitch + x) * kChunk + q * 4u;
-                *reinterpret_cast<v4f*>(dst) = acc[k];
+                TO* dst = DST_NHWC
+                              ? gcm + (((size_t)bimg * height + y) * width + x) * (size_t)C + (k0 + k) * kChunk + q * 4u
+                              : gcm + (((size_t)bimg * nchunks + (k0 + k)) * slice_px + (size_t)y * pitch + x) * kChunk + q * 4u;
+                store4(dst, acc[k]);
             }
         }
     }

@@ -268,3 +268,56 @@ __device__ __forceinline__ void buf_store1(__amdgpu_buffer_rsrc_t r, unsigned by
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, byte_off, 0, AUX);
 }
 
+// ------------------------------------------------------------------------------------
+// Element types of the CALLER's tensors (0.10.0): float, or bfloat16 / float16.  A 16-bit element is
+// widened exactly to fp32 where it is loaded, everything in between runs in fp32 as for float tensors, and a result is
+// rounded ONCE where it is stored: a plain conversion (v_cvt_pk_bf16_f32 / v_cvt_f16_f32: round to nearest even, a NaN
+// stays a NaN, -0.0 stays -0.0).  Workspace copies (chunk-major map, pixel-major top_diff, chunk-major gradient) are
+// fp32 whatever the caller's type.  For T = float every helper below is the plain fp32 access it replaces.
+// ------------------------------------------------------------------------------------
+typedef __bf16 bf16_t;
+typedef _Float16 fp16_t;
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
+template <class T> struct Vec4 { typedef T type __attribute__((ext_vector_type(4))); };
+
+template <class T>
+__device__ __forceinline__ float to_f32(T x) { return (float)x; }
+template <class T>
+__device__ __forceinline__ T from_f32(float x) { return (T)x; }
+
+// four consecutive elements at p (aligned to four elements) -> fp32; NT: a streaming load
+template <class T, bool NT = false>
+__device__ __forceinline__ v4f load4(const T* p)
+{
+    typedef typename Vec4<T>::type vt;
+    const vt v = NT ? __builtin_nontemporal_load(reinterpret_cast<const vt*>(p)) : *reinterpret_cast<const vt*>(p);
+    return __builtin_convertvector(v, v4f);
+}
+// fp32 -> four consecutive elements at p (aligned to four elements)
+template <class T>
+__device__ __forceinline__ void store4(T* p, v4f v)
+{
+    typedef typename Vec4<T>::type vt;
+    *reinterpret_cast<vt*>(p) = __builtin_convertvector(v, vt);
+}
+// the buffer-descriptor stores of the crops: four elements (16 bytes of float, 8 of a 16-bit type) / one element at
+// a BYTE offset the caller derives from the element index (kOOB, the sentinel, stays kOOB: it is never scaled)
+template <class T, int AUX>
+__device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, unsigned byte_off, v4f v)
+{
+    if constexpr (sizeof(T) == 4) {
+        buf_store<AUX>(r, byte_off, v);
+    } else {
+        typedef typename Vec4<T>::type vt;
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, __builtin_convertvector(v, vt)), r, byte_off, 0, AUX);
+    }
+}
+template <class T, int AUX>
+__device__ __forceinline__ void buf_store1(__amdgpu_buffer_rsrc_t r, unsigned byte_off, float v)
+{
+    if constexpr (sizeof(T) == 4)
+        buf_store1<AUX>(r, byte_off, v);
+    else
+        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, from_f32<T>(v)), r, byte_off, 0, AUX);
+}
+

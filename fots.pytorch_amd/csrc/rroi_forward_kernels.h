@@ -32,8 +32,9 @@ constexpr int kTP = kRelayoutPx + 4;
 // run -- instead of (image, chunk, pixel, 32).  The backward's copy of top_diff uses it: its gather
 // reads the 8 chunks of a bin together, and eight lines of one DRAM page cost less than eight lines 65 KB
 // apart (cfg3: gather 52 -> 39 us).
-template <int AUX, bool MASK, bool PIXMAJOR = false, class Live = NoLive>
-__device__ __forceinline__ void relayout_run(float* __restrict__ T, const float* __restrict__ nchw,
+// TS: the element type of the source (the caller's tensor); the copy is fp32 whatever it is.
+template <int AUX, bool MASK, bool PIXMAJOR = false, class Live = NoLive, class TS = float>
+__device__ __forceinline__ void relayout_run(float* __restrict__ T, const TS* __restrict__ nchw,
                                                float* __restrict__ cm, int C, int HW, int width, int pitch,
                                                FastDiv div_w, int nchunks, int ptiles, int first_tile,
                                                int tile_stride, int relayout_tiles,
@@ -57,7 +58,7 @@ __device__ __forceinline__ void relayout_run(float* __restrict__ T, const float*
     const int x4 = lane & 31, csub = lane >> 5;
     const int cq = lane & 7, pl = lane >> 3;
     // rows of 16-byte aligned float4 (p0 is a multiple of 128): needs HW % 4 == 0 and an aligned base
-    const bool vec_ok = (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(nchw) & 15) == 0;
+    const bool vec_ok = (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(nchw) & (4 * sizeof(TS) - 1)) == 0;
 
     // (MASK) highest live pooled column of image b: pw <= rpw  <=>  pw <= floor(rpw) for integer pw
     auto live_limit = [&](int b) -> float {
@@ -65,7 +66,10 @@ __device__ __forceinline__ void relayout_run(float* __restrict__ T, const float*
         return (A.batch >= 0 && A.batch < mask_batches) ? A.rpw : -1.0f;
     };
 
-    v4f r[4];
+    // the tile in flight is kept in the SOURCE's type and widened where it goes into LDS: a conversion right behind the
+    // load would make the load wait there, and the next tile's loads would no longer overlap the current tile's stores
+    typedef typename Vec4<TS>::type vraw;
+    vraw r[4];
     auto load_tile = [&](int tile) {
         // chunk index fastest: with the grid a multiple of nchunks a block always relays out
         // the same chunk, i.e. (8 chunks, blocks dealt round-robin to the 8 XCDs) slice k is
@@ -74,7 +78,7 @@ __device__ __forceinline__ void relayout_run(float* __restrict__ T, const float*
         const int pt = (tile / nchunks) % ptiles;
         const int b = tile / (ptiles * nchunks);
         const int p0 = pt * kRelayoutPx, c0 = k * kChunk;
-        const float* src = nchw + ((size_t)b * C + c0) * HW + p0;
+        const TS* src = nchw + ((size_t)b * C + c0) * HW + p0;
         const int p = 4 * x4;
         bool live = true;
         if (MASK) {
@@ -99,14 +103,14 @@ __device__ __forceinline__ void relayout_run(float* __restrict__ T, const float*
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int c = w * 8 + i * 2 + csub;
-            v4f v = {0.f, 0.f, 0.f, 0.f};
+            vraw v = {0, 0, 0, 0};
             if (c0 + c < C && live) {
-                const float* sp = src + (size_t)c * HW + p;
+                const TS* sp = src + (size_t)c * HW + p;
                 if (vec_ok && p0 + p + 3 < HW) {
                     // PIXMAJOR (the backward's top_diff): read once, streaming -- the copy, not the source,
                     // should be what the memory-side cache holds when the gather starts
-                    v = PIXMAJOR ? __builtin_nontemporal_load(reinterpret_cast<const v4f*>(sp))
-                                 : *reinterpret_cast<const v4f*>(sp);
+                    v = PIXMAJOR ? __builtin_nontemporal_load(reinterpret_cast<const vraw*>(sp))
+                                 : *reinterpret_cast<const vraw*>(sp);
                 } else {
                     if (p0 + p + 0 < HW) v.x = sp[0];
                     if (p0 + p + 1 < HW) v.y = sp[1];
@@ -141,7 +145,7 @@ __device__ __forceinline__ void relayout_run(float* __restrict__ T, const float*
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int c = w * 8 + i * 2 + csub;
-            *reinterpret_cast<v4f*>(T + c * kTP + ((4 * x4) ^ ((c >> 3) * 4))) = r[i];
+            *reinterpret_cast<v4f*>(T + c * kTP + ((4 * x4) ^ ((c >> 3) * 4))) = __builtin_convertvector(r[i], v4f);
         }
         __syncthreads();
         const int cur = tile;
@@ -184,7 +188,8 @@ __device__ __forceinline__ void relayout_run(float* __restrict__ T, const float*
 }
 
 // one (roi, bin) over the channels [c_begin, c_end): geometry once, then the reference's four taps per channel
-__device__ __forceinline__ void direct_bin(const float* __restrict__ feat, const Affine& A, float* __restrict__ out,
+template <class TI, class TO>
+__device__ __forceinline__ void direct_bin(const TI* __restrict__ feat, const Affine& A, TO* __restrict__ out,
                                            float* __restrict__ idx_x, float* __restrict__ idx_y, int n, int bin, int C,
                                            int height, int width, int pooled_width, int NB, int batch_size,
                                            int c_begin, int c_end)
@@ -205,18 +210,18 @@ __device__ __forceinline__ void direct_bin(const float* __restrict__ feat, const
     const unsigned o_rb = o_lb + ((f & kDx) ? 1u : 0u);
 
     const size_t HW = (size_t)height * width;
-    const float* plane = feat + ((size_t)(batch_ok ? A.batch : 0) * C + c_begin) * HW;
+    const TI* plane = feat + ((size_t)(batch_ok ? A.batch : 0) * C + c_begin) * HW;
     size_t o = ((size_t)n * C + c_begin) * NB + bin;
     for (int c = c_begin; c < c_end; ++c, plane += HW, o += NB) {
         float v = 0.0f;
         if (active) {
-            const float lt = (f & kV00) ? plane[o_lt] : 0.0f;
-            const float rt = (f & kV01) ? plane[o_rt] : 0.0f;
-            const float lb = (f & kV10) ? plane[o_lb] : 0.0f;
-            const float rb = (f & kV11) ? plane[o_rb] : 0.0f;
+            const float lt = (f & kV00) ? to_f32(plane[o_lt]) : 0.0f;
+            const float rt = (f & kV01) ? to_f32(plane[o_rt]) : 0.0f;
+            const float lb = (f & kV10) ? to_f32(plane[o_lb]) : 0.0f;
+            const float rb = (f & kV11) ? to_f32(plane[o_rb]) : 0.0f;
             v = blend1(lt, rt, rb, lb, wlt, wrt, wrb, wlb);
         }
-        out[o] = v;
+        out[o] = from_f32<TO>(v);
         if (idx_x) idx_x[o] = active ? bcx : 0.0f;
         if (idx_y) idx_y[o] = active ? bcy : 0.0f;
     }
@@ -313,9 +318,10 @@ __device__ __forceinline__ void rroi_sort_rois(unsigned* hist, const float* __re
     for (int n = tid + kSortRegs * 256; n < num_rois; n += 256) order[hist[key_of(n)] + (unsigned)rank[n]] = n;
 }
 
-template <int AUX>
+// TS: the element type of the caller's map (the launcher's rest-of-the-images blocks: float only)
+template <int AUX, class TS = float>
 __global__ __launch_bounds__(256) void rroi_prologue_kernel(
-    const float* __restrict__ nchw, float* __restrict__ cm, int C, int HW, int width, int pitch,
+    const TS* __restrict__ nchw, float* __restrict__ cm, int C, int HW, int width, int pitch,
     FastDiv div_w, int nchunks, int ptiles, int relayout_blocks, int relayout_tiles,
     int batch_size, const float* __restrict__ rois, int num_rois, int pooled_height,
     float spatial_scale, int trig, Affine* __restrict__ aff, int aff_blocks = 0, float* __restrict__ rest_out = nullptr,
@@ -331,7 +337,7 @@ __global__ __launch_bounds__(256) void rroi_prologue_kernel(
                        sort_order);
         return;
     }
-    if (rest_out && (int)blockIdx.x >= relayout_blocks + aff_blocks + sort_blocks) {
+    if (std::is_same<TS, float>::value && rest_out && (int)blockIdx.x >= relayout_blocks + aff_blocks + sort_blocks) {
         // The reference-ABI launcher (one more block per ROI).  Its signature does not say how many images
         // `nchw` holds, so the copy and the tiled gather serve image 0; the ROIs of images >= 1 -- none, as a
         // rule: the block reads the index and leaves -- are sampled here from the NCHW tensor, trusting the
@@ -340,8 +346,9 @@ __global__ __launch_bounds__(256) void rroi_prologue_kernel(
         if (f2i_sat(rois[(size_t)n * 6]) < batch_size) return;
         const Affine A = make_affine(rois + (size_t)n * 6, pooled_height, spatial_scale, trig);
         const int NB = pooled_height * pooled_width;
-        for (int bin = tid; bin < NB; bin += 256)
-            direct_bin(nchw, A, rest_out, nullptr, nullptr, n, bin, C, HW / width, width, pooled_width, NB, /*trust*/ -1, 0, C);
+        if constexpr (std::is_same<TS, float>::value)
+            for (int bin = tid; bin < NB; bin += 256)
+                direct_bin(nchw, A, rest_out, nullptr, nullptr, n, bin, C, HW / width, width, pooled_width, NB, /*trust*/ -1, 0, C);
         return;
     }
     if ((int)blockIdx.x >= relayout_blocks) {
@@ -436,9 +443,10 @@ struct RoiSource {   // NCHW_SRC: where the storer takes its affines from
     float spatial_scale;
     int trig;
 };
-template <bool VEC_STORE, int EARLY, int OCC, int HID, bool ONHWC, int SHIFT, bool NCHW_SRC = false, int WAUX = -1>
+template <bool VEC_STORE, int EARLY, int OCC, int HID, bool ONHWC, int SHIFT, bool NCHW_SRC = false, int WAUX = -1,
+          class TO = float>
 __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
-    const float* __restrict__ map, const Affine* __restrict__ aff, float* __restrict__ out,
+    const float* __restrict__ map, const Affine* __restrict__ aff, TO* __restrict__ out,
     int num_rois, int C, int height, int width, int pooled_width, int NB, int batch_size,
     int nchunks, int ntiles, SliceLayout lay, FastDiv div_tiles, FastDiv div_pw, int dbg, XcdGroups xg,
     RoiSource roi_src = RoiSource{nullptr, 0, 0.0f, 0})
@@ -455,6 +463,8 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
     // two classes, each padded to a multiple of 8: ceil(a/8) + ceil(b/8) <= 9 for a + b <= 64 (and one
     // forced LO group + 8 HI groups when a = 0)
     constexpr int kMaxGroups = kIters + 1;
+    // bytes of one crop element: offsets below are ELEMENT indices times kEs (the sentinel kOOB is never scaled)
+    constexpr unsigned kEs = (unsigned)sizeof(TO);
     // LO groups whose loads are issued before barrier 2, besides the first one (0 in the NCHW forms: no difference
     // measured with the loads in a wave of their own; 2 in the channels-last form, round 3's first shape)
     constexpr int kEarly = EARLY;
@@ -689,8 +699,8 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
             }
             wg_lds_barrier();  // T has been read
             const bool live = !(dbg & 1) && !skip;
-            float* obase = out + (size_t)n * NB * C;
-            const __amdgpu_buffer_rsrc_t ws = make_rsrc(obase, (unsigned)NB * (unsigned)C * 4u);
+            TO* obase = out + (size_t)n * NB * C;
+            const __amdgpu_buffer_rsrc_t ws = make_rsrc(obase, (unsigned)NB * (unsigned)C * kEs);
             const bool q_ok = k * kChunk + q * 4 < (unsigned)C;
 #pragma unroll
             for (int it8 = 0; it8 < kIters; ++it8) {
@@ -698,10 +708,10 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
                 const bool on = (cur_mask >> bl) & 1ull;
                 const v4f o = {on ? c[it8].x : 0.f, on ? c[it8].y : 0.f, on ? c[it8].z : 0.f, on ? c[it8].w : 0.f};
                 const unsigned bin = t * kTileBins + bl;
-                const unsigned off = (bin * (unsigned)C + k * kChunk + q * 4u) * 4u;
+                const unsigned off = (bin * (unsigned)C + k * kChunk + q * 4u) * kEs;
                 const unsigned o_off = (live && q_ok && bin < (unsigned)NB) ? off : kOOB;
-                if (it8 < kMinorStores) buf_store<kMinorAux>(ws, o_off, o);
-                else buf_store<kStoreAux>(ws, o_off, o);
+                if (it8 < kMinorStores) buf_store4<TO, kMinorAux>(ws, o_off, o);
+                else buf_store4<TO, kStoreAux>(ws, o_off, o);
             }
             return;
         }
@@ -714,8 +724,8 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
         wg_lds_barrier();  // T has been read: the gatherer may blend the next tile into it
         const bool live = !(dbg & 1) && !skip;
         // descriptor over this (roi, chunk) block of the output: rows >= C fall out of range
-        float* obase = out + ((size_t)n * C + k * kChunk) * NB;
-        const __amdgpu_buffer_rsrc_t ws = make_rsrc(obase, chans_here * (unsigned)NB * 4u);
+        TO* obase = out + ((size_t)n * C + k * kChunk) * NB;
+        const __amdgpu_buffer_rsrc_t ws = make_rsrc(obase, chans_here * (unsigned)NB * kEs);
         const unsigned bin0 = t * kTileBins + col;
         // bins that were in no group (masked by pw > roi_pooled_width) are zero
         const unsigned nib = (unsigned)(cur_mask >> col) & 15u;
@@ -723,7 +733,7 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
 #pragma unroll
         for (int s4 = 0; s4 < kChunk / 4; ++s4) {
             const unsigned r = s4 * 4 + row0;
-            const unsigned off = (r * (unsigned)NB + bin0) * 4u;
+            const unsigned off = (r * (unsigned)NB + bin0) * kEs;
             const v4f o = {a0 ? v[s4].x : 0.f, a1 ? v[s4].y : 0.f, a2 ? v[s4].z : 0.f, a3 ? v[s4].w : 0.f};
             if (VEC_STORE) {  // NB % 4 == 0: the 4 bins are all inside or all outside the row
                 // WAUX >= 0: ONE policy for all eight stores (the merging form for rows that are not whole sectors, see the host)
@@ -731,22 +741,22 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
                     // any NB: a quad wholly inside the row is ONE 16-byte store (dword-aligned: the rows of such crops start
                     // anywhere); the row's last quad, when NB % 4 != 0, leaves as its <= 3 valid dwords -- in a row's last tile only
                     constexpr int A = WAUX >= 0 ? WAUX : 0;
-                    buf_store<A>(ws, (live && bin0 + 4u <= (unsigned)NB) ? off : kOOB, o);
+                    buf_store4<TO, A>(ws, (live && bin0 + 4u <= (unsigned)NB) ? off : kOOB, o);
                     if (t == (unsigned)ntiles - 1u && ((unsigned)NB & 3u)) {   // (wave-uniform)
                         const bool part = live && bin0 < (unsigned)NB && bin0 + 4u > (unsigned)NB;
-                        buf_store1<A>(ws, part ? off + 0 : kOOB, o.x);
-                        buf_store1<A>(ws, (part && bin0 + 1 < (unsigned)NB) ? off + 4 : kOOB, o.y);
-                        buf_store1<A>(ws, (part && bin0 + 2 < (unsigned)NB) ? off + 8 : kOOB, o.z);
+                        buf_store1<TO, A>(ws, part ? off + 0 : kOOB, o.x);
+                        buf_store1<TO, A>(ws, (part && bin0 + 1 < (unsigned)NB) ? off + kEs : kOOB, o.y);
+                        buf_store1<TO, A>(ws, (part && bin0 + 2 < (unsigned)NB) ? off + 2 * kEs : kOOB, o.z);
                     }
                 } else if (s4 < kMinorStores)
-                    buf_store<kMinorAux>(ws, (live && bin0 < (unsigned)NB) ? off : kOOB, o);
+                    buf_store4<TO, kMinorAux>(ws, (live && bin0 < (unsigned)NB) ? off : kOOB, o);
                 else
-                    buf_store<kStoreAux>(ws, (live && bin0 < (unsigned)NB) ? off : kOOB, o);
+                    buf_store4<TO, kStoreAux>(ws, (live && bin0 < (unsigned)NB) ? off : kOOB, o);
             } else {
-                buf_store1<kStoreAux>(ws, (live && bin0 + 0 < (unsigned)NB) ? off + 0 : kOOB, o.x);
-                buf_store1<kStoreAux>(ws, (live && bin0 + 1 < (unsigned)NB) ? off + 4 : kOOB, o.y);
-                buf_store1<kStoreAux>(ws, (live && bin0 + 2 < (unsigned)NB) ? off + 8 : kOOB, o.z);
-                buf_store1<kStoreAux>(ws, (live && bin0 + 3 < (unsigned)NB) ? off + 12 : kOOB, o.w);
+                buf_store1<TO, kStoreAux>(ws, (live && bin0 + 0 < (unsigned)NB) ? off + 0 : kOOB, o.x);
+                buf_store1<TO, kStoreAux>(ws, (live && bin0 + 1 < (unsigned)NB) ? off + kEs : kOOB, o.y);
+                buf_store1<TO, kStoreAux>(ws, (live && bin0 + 2 < (unsigned)NB) ? off + 2 * kEs : kOOB, o.z);
+                buf_store1<TO, kStoreAux>(ws, (live && bin0 + 3 < (unsigned)NB) ? off + 3 * kEs : kOOB, o.w);
             }
         }
     };
@@ -787,8 +797,9 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
         // instruction, and the stores took the TCP from the gatherer's tap loads (tools/kbench desync, PMC)
         const unsigned ch16 = lane >> 2, pcl = lane & 3u;
         const unsigned nb15 = (unsigned)NB & 15u;
-        // float index of (roi n, first channel of the chunk, bin 0), modulo a sector -- out's own alignment included
-        const unsigned h0 = (((unsigned)(reinterpret_cast<size_t>(out) >> 2) & 15u) +
+        // element index of (roi n, first channel of the chunk, bin 0), modulo 16 -- out's own alignment included (a
+        // window of 16 elements: one 64-byte sector of float crops, half a sector of 16-bit crops)
+        const unsigned h0 = (((unsigned)(reinterpret_cast<size_t>(out) / sizeof(TO)) & 15u) +
                              (((n & 15u) * ((unsigned)C & 15u) + ((k * kChunk) & 15u)) & 15u) * nb15) & 15u;
         const unsigned h = (h0 + ch16 * nb15) & 15u;           // of both channels of this lane
         const int left = NB - (int)(t * (unsigned)kOwnBins);   // bins of the row from this tile's own first on (>= 1)
@@ -825,8 +836,8 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
         }
         wg_lds_barrier();  // T has been read: the gatherer may blend the next tile into it
         const bool live = !(dbg & 1) && !skip;
-        float* obase = out + ((size_t)n * C + k * kChunk) * NB;
-        const __amdgpu_buffer_rsrc_t ws = make_rsrc(obase, chans_here * (unsigned)NB * 4u);
+        TO* obase = out + ((size_t)n * C + k * kChunk) * NB;
+        const __amdgpu_buffer_rsrc_t ws = make_rsrc(obase, chans_here * (unsigned)NB * kEs);
         const int rl = first ? (int)h : 0, rh = last ? left + (int)h : kOwnBins;
         const unsigned msh = 16u + 4u * pcl - h;                // the lane that gathered this lane's first element of sector 0
 #pragma unroll
@@ -839,10 +850,10 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
             const v4f v = {(nib & 1u) ? o[i].x : 0.f, (nib & 2u) ? o[i].y : 0.f, (nib & 4u) ? o[i].z : 0.f,
                            (nib & 8u) ? o[i].w : 0.f};
             const bool whole = p0 >= rl && p0 + 4 <= rh;
-            // float offset of position p0 within the (roi, chunk) block; never negative where `whole`
-            const unsigned off = (r * (unsigned)NB + t * (unsigned)kOwnBins + (unsigned)p0 - h) * 4u;
+            // element offset of position p0 within the (roi, chunk) block; never negative where `whole`
+            const unsigned off = (r * (unsigned)NB + t * (unsigned)kOwnBins + (unsigned)p0 - h) * kEs;
             const unsigned o_off = (live && whole && r < chans_here) ? off : kOOB;
-            buf_store<kShiftAux>(ws, o_off, v);
+            buf_store4<TO, kShiftAux>(ws, o_off, v);
         }
         if (first || last) {
 #pragma unroll
@@ -850,8 +861,8 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
                 const int pa = pl + (int)fi + 2 * ps, pb = (ph & ~3) + (int)fi + 2 * ps;
                 const bool oka = live && fr < chans_here && pa < ((pl + 3) & ~3) && pa < ph;
                 const bool okb = live && fr < chans_here && pb < ph && pb >= pl && (ph & ~3) >= ((pl + 3) & ~3);
-                buf_store1<kShiftAux>(ws, oka ? (fr * (unsigned)NB + t * (unsigned)kOwnBins + (unsigned)pa - fh) * 4u : kOOB, fix[ps]);
-                buf_store1<kShiftAux>(ws, okb ? (fr * (unsigned)NB + t * (unsigned)kOwnBins + (unsigned)pb - fh) * 4u : kOOB, fix[2 + ps]);
+                buf_store1<TO, kShiftAux>(ws, oka ? (fr * (unsigned)NB + t * (unsigned)kOwnBins + (unsigned)pa - fh) * kEs : kOOB, fix[ps]);
+                buf_store1<TO, kShiftAux>(ws, okb ? (fr * (unsigned)NB + t * (unsigned)kOwnBins + (unsigned)pb - fh) * kEs : kOOB, fix[2 + ps]);
             }
         }
     };
@@ -867,7 +878,7 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
     auto drain_shift2 = [&](unsigned n, unsigned t, unsigned long long cur_mask, bool skip) {
         const unsigned row8 = lane >> 3, pc = lane & 7u;
         const unsigned nb31 = (unsigned)NB & 31u;
-        const unsigned h0 = (((unsigned)(reinterpret_cast<size_t>(out) >> 2) & 31u) +
+        const unsigned h0 = (((unsigned)(reinterpret_cast<size_t>(out) / sizeof(TO)) & 31u) +
                              (((n & 31u) * ((unsigned)C & 31u)) & 31u) * nb31) & 31u;   // (k * 32 channels: whole lines)
         const int left = NB - (int)(t * (unsigned)kOwnBins);
         const bool first = t == 0, last = left <= kOwnBins;
@@ -903,8 +914,8 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
         }
         wg_lds_barrier();  // T has been read: the gatherer may blend the next tile into it
         const bool live = !(dbg & 1) && !skip;
-        float* obase = out + ((size_t)n * C + k * kChunk) * NB;
-        const __amdgpu_buffer_rsrc_t ws = make_rsrc(obase, chans_here * (unsigned)NB * 4u);
+        TO* obase = out + ((size_t)n * C + k * kChunk) * NB;
+        const __amdgpu_buffer_rsrc_t ws = make_rsrc(obase, chans_here * (unsigned)NB * kEs);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             if ((i >> 2) == 1 && !last) continue;
@@ -917,8 +928,8 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
             const v4f v = {(nib & 1u) ? o[i].x : 0.f, (nib & 2u) ? o[i].y : 0.f, (nib & 4u) ? o[i].z : 0.f,
                            (nib & 8u) ? o[i].w : 0.f};
             const bool whole = p0 >= rl && p0 + 4 <= rh;
-            const unsigned off = (r * (unsigned)NB + t * (unsigned)kOwnBins + (unsigned)p0 - h) * 4u;
-            buf_store<kShift2Aux>(ws, (live && whole && r < chans_here) ? off : kOOB, v);
+            const unsigned off = (r * (unsigned)NB + t * (unsigned)kOwnBins + (unsigned)p0 - h) * kEs;
+            buf_store4<TO, kShift2Aux>(ws, (live && whole && r < chans_here) ? off : kOOB, v);
         }
         if (first || last) {
 #pragma unroll
@@ -926,8 +937,8 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
                 const int pa = pl + (int)fi + 2 * ps, pb = (ph & ~3) + (int)fi + 2 * ps;
                 const bool oka = live && fr < chans_here && pa < ((pl + 3) & ~3) && pa < ph;
                 const bool okb = live && fr < chans_here && pb < ph && pb >= pl && (ph & ~3) >= ((pl + 3) & ~3);
-                buf_store1<kShift2Aux>(ws, oka ? (fr * (unsigned)NB + t * (unsigned)kOwnBins + (unsigned)pa - fh) * 4u : kOOB, fix[ps]);
-                buf_store1<kShift2Aux>(ws, okb ? (fr * (unsigned)NB + t * (unsigned)kOwnBins + (unsigned)pb - fh) * 4u : kOOB, fix[2 + ps]);
+                buf_store1<TO, kShift2Aux>(ws, oka ? (fr * (unsigned)NB + t * (unsigned)kOwnBins + (unsigned)pa - fh) * kEs : kOOB, fix[ps]);
+                buf_store1<TO, kShift2Aux>(ws, okb ? (fr * (unsigned)NB + t * (unsigned)kOwnBins + (unsigned)pb - fh) * kEs : kOOB, fix[2 + ps]);
             }
         }
     };
@@ -1101,8 +1112,9 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
 // Used for small R (where relaying out the whole map would dominate) and by the
 // reference-ABI launcher; optionally writes the reference's con_idx_x / con_idx_y.
 // ------------------------------------------------------------------------------------
+template <class T = float>
 __global__ __launch_bounds__(256) void rroi_fwd_direct_kernel(
-    const float* __restrict__ feat, const float* __restrict__ rois, float* __restrict__ out,
+    const T* __restrict__ feat, const float* __restrict__ rois, T* __restrict__ out,
     float* __restrict__ idx_x, float* __restrict__ idx_y, int num_rois, int C, int height,
     int width, int pooled_height, int pooled_width, float spatial_scale, int trig, int batch_size,
     int cslab)
@@ -1145,9 +1157,10 @@ constexpr unsigned kPairShift = 1u << 20;
 
 // WITH_IDX: also the reference ABI's con_idx_x / con_idx_y (kernel.cu:144-145); batch_size < 0 = unknown (that ABI): the
 // image index is trusted as the reference trusts it.
-template <int U, bool WITH_IDX = false>
+// T: the element type of the map and the crops (a row pair of a 16-bit map is one 4-byte load)
+template <int U, bool WITH_IDX = false, class T = float>
 __global__ __launch_bounds__(256) void rroi_fwd_patch_kernel(
-    const float* __restrict__ feat, const float* __restrict__ rois, float* __restrict__ out, int num_rois, int C, int height,
+    const T* __restrict__ feat, const float* __restrict__ rois, T* __restrict__ out, int num_rois, int C, int height,
     int width, int pooled_height, int pooled_width, float spatial_scale, int trig, int batch_size, int cwave, int npx,
     int npatches, int prows, int pcols, float* __restrict__ idx_x = nullptr, float* __restrict__ idx_y = nullptr)
 {
@@ -1169,7 +1182,8 @@ __global__ __launch_bounds__(256) void rroi_fwd_patch_kernel(
         const bool in_rroi = bin_centre(A, ph, pw, height, width, bcx, bcy);
         const bool batch_ok = batch_size < 0 || (A.batch >= 0 && A.batch < batch_size);
         const bool active = in_rroi && batch_ok && inside;
-        const Taps tp = make_taps(bcx, bcy, active, height, width, 4u);   // byte offsets inside a channel plane
+        constexpr unsigned kEs = (unsigned)sizeof(T);
+        const Taps tp = make_taps(bcx, bcy, active, height, width, kEs);   // byte offsets inside a channel plane
         const unsigned f = tp.flags;
         const bool dx = f & kDx, dy = f & kDy;
         // a row's pair is fetched when one of its two pixels is a valid tap OF ITS OWN (an aliased tap copies)
@@ -1177,10 +1191,10 @@ __global__ __launch_bounds__(256) void rroi_fwd_patch_kernel(
         const bool bot = dy && ((f & kV10) || (dx && (f & kV11)));
         // x0 is the row's last pixel: the pair starts one pixel earlier (x1 = W is never a valid tap)
         const bool shift = (f & kActive) && f2i_sat(floorf(bcx)) == width - 1 && width >= 2;
-        const unsigned o0 = tp.o_lt - (shift ? 4u : 0u);
+        const unsigned o0 = tp.o_lt - (shift ? kEs : 0u);
         PatchRec r;
         r.o_top = top ? o0 : kOOB;
-        r.o_bot = bot ? o0 + (unsigned)width * 4u : kOOB;
+        r.o_bot = bot ? o0 + (unsigned)width * kEs : kOOB;
         r.flags = f | (shift ? kPairShift : 0u);
         r.rx = tp.rx;
         r.ry = tp.ry;
@@ -1202,13 +1216,19 @@ __global__ __launch_bounds__(256) void rroi_fwd_patch_kernel(
     tap_weights(r.rx, r.ry, wlt, wrt, wrb, wlb);
     const int NB = pooled_height * pooled_width;
     const size_t HW = (size_t)height * width;
-    const unsigned plane_bytes = (unsigned)(HW * 4u);
-    const float* plane = feat + ((size_t)batch * C + c_begin) * HW;
+    const unsigned plane_bytes = (unsigned)(HW * sizeof(T));
+    const T* plane = feat + ((size_t)batch * C + c_begin) * HW;
     const size_t o0 = ((size_t)n * C + c_begin) * NB + (size_t)ph * pooled_width + pw;
-    float* op = out + o0;
+    T* op = out + o0;
     typedef float v2f __attribute__((ext_vector_type(2)));
-    auto pair = [&](const float* pl, unsigned o) -> v2f {
-        return __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(make_rsrc(pl, plane_bytes), o, 0, 0));
+    auto pair = [&](const T* pl, unsigned o) -> v2f {
+        if constexpr (sizeof(T) == 4) {
+            return __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(make_rsrc(pl, plane_bytes), o, 0, 0));
+        } else {
+            typedef T v2t __attribute__((ext_vector_type(2)));
+            const v2t h = __builtin_bit_cast(v2t, __builtin_amdgcn_raw_buffer_load_b32(make_rsrc(pl, plane_bytes), o, 0, 0));
+            return __builtin_convertvector(h, v2f);
+        }
     };
     auto sample = [&](v2f t, v2f b) -> float {
         // the reference's four taps (kernel.cu:110-126) out of the two pairs: element 0 is x0 (element 1 when the pair was
@@ -1230,12 +1250,12 @@ __global__ __launch_bounds__(256) void rroi_fwd_patch_kernel(
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const float v = sample(t[u], b[u]);
-            if (inside) op[(size_t)u * NB] = v;
+            if (inside) op[(size_t)u * NB] = from_f32<T>(v);
         }
     }
     for (; c < c_end; ++c, plane += HW, op += NB) {
         const float v = sample(pair(plane, r.o_top), pair(plane, r.o_bot));
-        if (inside) *op = v;
+        if (inside) *op = from_f32<T>(v);
     }
     if (WITH_IDX && inside) {
         for (int cc = 0; cc < c_end - c_begin; ++cc) {

@@ -39,6 +39,11 @@ PLAN_BWD_DIRECT, PLAN_BWD_ATOMIC, PLAN_BWD_INKERNEL, PLAN_BWD_LISTS, PLAN_BWD_BU
 PLAN_KERNEL_STRIDED, PLAN_KERNEL_CHANNELS_LAST, PLAN_KERNEL_SHIFT, PLAN_KERNEL_STRIDED_MERGE, PLAN_KERNEL_SHIFT_LINES = 0, 1, 2, 3, 4
 PLAN_DST_NONE, PLAN_DST_CHUNK_MAJOR, PLAN_DST_NCHW, PLAN_DST_NCHW_ADD, PLAN_DST_NHWC = 0, 1, 2, 3, 4
 
+# element types of the features / crops (forward) and grad_output / gradient (backward), 0.10.0: the `dtype` argument of
+# the typed entry points.  rois are float32 in every case.
+DTYPE_FP32, DTYPE_BF16, DTYPE_FP16 = 0, 1, 2
+_DTYPES = {torch.float32: DTYPE_FP32, torch.bfloat16: DTYPE_BF16, torch.float16: DTYPE_FP16}
+
 if not os.path.exists(LIB_PATH):
     raise ImportError(
         f"{LIB_PATH} is missing: build it with `make -C fots.pytorch_amd/csrc` "
@@ -105,6 +110,14 @@ _lib.rroi_align_forward_plan.restype = _i
 _lib.rroi_align_forward_plan.argtypes = [_i] * 11 + [ctypes.POINTER(_Plan)]
 _lib.rroi_align_backward_plan.restype = _i
 _lib.rroi_align_backward_plan.argtypes = [_i] * 11 + [ctypes.POINTER(_Plan)]
+_lib.rroi_align_forward_plan_typed.restype = _i
+_lib.rroi_align_forward_plan_typed.argtypes = [_i] * 12 + [ctypes.POINTER(_Plan)]
+_lib.rroi_align_backward_plan_typed.restype = _i
+_lib.rroi_align_backward_plan_typed.argtypes = [_i] * 12 + [ctypes.POINTER(_Plan)]
+_lib.rroi_align_forward_typed_hip.restype = _i
+_lib.rroi_align_forward_typed_hip.argtypes = [_vp, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _vp]
+_lib.rroi_align_backward_typed_hip.restype = _i
+_lib.rroi_align_backward_typed_hip.argtypes = [_vp, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _vp]
 
 EXPORTS = (
     "RROIAlignForwardLaucher", "RROIAlignBackwardLaucher", "rroi_align_forward_hip",
@@ -117,6 +130,8 @@ EXPORTS = (
     "rroi_align_write_probe_hip", "rroi_align_launcher_scratch_stats",
     "rroi_align_set_trig_recipe_hip", "rroi_align_get_trig_recipe_hip",   # deprecated shims (refuse TRIG_FP32)
     "rroi_align_forward_plan", "rroi_align_backward_plan",
+    "rroi_align_forward_typed_hip", "rroi_align_backward_typed_hip",
+    "rroi_align_forward_plan_typed", "rroi_align_backward_plan_typed",
 )
 
 # What a call launches (rroi_align_forward_plan / rroi_align_backward_plan); the fields of rroi_align_plan.
@@ -130,24 +145,40 @@ def _plan(fn, args, what):
     return Plan(*(getattr(p, n) for n in Plan._fields))
 
 
+def dtype_code(dtype) -> int:
+    """DTYPE_* of a torch dtype (float32, bfloat16, float16) or of a DTYPE_* value; TypeError for anything else."""
+    if isinstance(dtype, torch.dtype):
+        if dtype not in _DTYPES:
+            raise TypeError(f"rroi_align takes float32, bfloat16 or float16 tensors, got {dtype}")
+        return _DTYPES[dtype]
+    return int(dtype)
+
+
 def forward_plan(batch_size, channels, height, width, num_rois, pooled_height, pooled_width,
                  feature_layout=LAYOUT_NCHW, top_layout=LAYOUT_NCHW, path=PATH_AUTO, caller=CALLER_NATIVE,
-                 trig=0) -> Plan:
+                 trig=0, dtype=DTYPE_FP32) -> Plan:
     """The plan a forward call with these arguments runs (host only, no GPU needed); ValueError where the call
-    would refuse them."""
-    return _plan(_lib.rroi_align_forward_plan,
-                 (feature_layout, top_layout, batch_size, num_rois, height, width, channels, pooled_height, pooled_width,
-                  _path_word(path, trig), caller), "rroi_align_forward_plan")
+    would refuse them.  dtype: of the features and crops (a torch dtype or DTYPE_*; the default is the fp32 query)."""
+    code = dtype_code(dtype)
+    args = (feature_layout, top_layout, batch_size, num_rois, height, width, channels, pooled_height, pooled_width,
+            _path_word(path, trig), caller)
+    if code == DTYPE_FP32:
+        return _plan(_lib.rroi_align_forward_plan, args, "rroi_align_forward_plan")
+    return _plan(_lib.rroi_align_forward_plan_typed, (code,) + args, "rroi_align_forward_plan_typed")
 
 
 def backward_plan(batch_size, channels, height, width, num_rois, pooled_height, pooled_width,
                   top_diff_layout=LAYOUT_NCHW, bottom_diff_layout=LAYOUT_NCHW, path=PATH_AUTO, caller=CALLER_NATIVE,
-                  trig=0) -> Plan:
+                  trig=0, dtype=DTYPE_FP32) -> Plan:
     """The plan a backward call with these arguments runs (host only, no GPU needed); ValueError where the call
-    would refuse them."""
-    return _plan(_lib.rroi_align_backward_plan,
-                 (top_diff_layout, bottom_diff_layout, batch_size, num_rois, height, width, channels, pooled_height,
-                  pooled_width, _path_word(path, trig), caller), "rroi_align_backward_plan")
+    would refuse them.  dtype: of grad_output and the gradient (a torch dtype or DTYPE_*; the default is the fp32
+    query)."""
+    code = dtype_code(dtype)
+    args = (top_diff_layout, bottom_diff_layout, batch_size, num_rois, height, width, channels, pooled_height,
+            pooled_width, _path_word(path, trig), caller)
+    if code == DTYPE_FP32:
+        return _plan(_lib.rroi_align_backward_plan, args, "rroi_align_backward_plan")
+    return _plan(_lib.rroi_align_backward_plan_typed, (code,) + args, "rroi_align_backward_plan_typed")
 
 
 def version() -> str:
@@ -228,15 +259,18 @@ def launcher_scratch_stats() -> dict:
     return {"in_use": u.value, "pinned": p.value, "capacity": c.value, "transient_calls": t.value}
 
 
-def _require_cuda_f32(t: torch.Tensor, name: str) -> None:
+def _require_cuda_f32(t: torch.Tensor, name: str, dtypes=(torch.float32,)) -> None:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
     if not t.is_cuda:
         raise RuntimeError(
             f"{name} is on {t.device}: rroi_align runs on the GPU only (the reference's CPU "
             "branch, functions/rroi_align.py:22-25, is dead code and is not reproduced)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, got {t.dtype}")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name} must be {' or '.join(str(d).replace('torch.', '') for d in dtypes)}, got {t.dtype}")
+
+
+_IO_DTYPES = (torch.float32, torch.bfloat16, torch.float16)   # features / crops, grad_output / gradient
 
 
 # --------------------------------------------------------------------------- native path
@@ -246,10 +280,14 @@ def forward(features: torch.Tensor, rois: torch.Tensor, pooled_height: int, pool
     """(B,C,H,W) x (R,6) -> (R,C,PH,PW).  NCHW-contiguous or channels_last features.
     channels_last_out: return the crops in channels_last storage (same values) for a recognition
     head that runs in channels_last; needs C % 4 == 0 and the tiled path.
-    trig: TRIG_DOUBLE / TRIG_FP32, for this call (pass the same to backward())."""
+    trig: TRIG_DOUBLE / TRIG_FP32, for this call (pass the same to backward()).
+    features: float32, bfloat16 or float16 -- the crops have the same dtype (a 16-bit call computes in fp32 and rounds
+    each crop element once: bit for bit the fp32 call on the widened map, rounded; channels_last 16-bit features are
+    made contiguous first, PATH_FUSED is fp32 only).  rois: float32."""
     word = _path_word(path, trig)
-    _require_cuda_f32(features, "features")
+    _require_cuda_f32(features, "features", _IO_DTYPES)
     _require_cuda_f32(rois, "rois")
+    code = _DTYPES[features.dtype]
     if features.dim() != 4:
         raise ValueError(f"features must be (B,C,H,W), got {tuple(features.shape)}")
     if rois.dim() != 2 or rois.size(1) != 6:
@@ -263,7 +301,8 @@ def forward(features: torch.Tensor, rois: torch.Tensor, pooled_height: int, pool
         raise ValueError("pooled_height and pooled_width must be positive")
     if features.is_contiguous():
         layout = LAYOUT_NCHW
-    elif features.is_contiguous(memory_format=torch.channels_last) and C % 4 == 0 and path not in (PATH_DIRECT, PATH_FUSED):
+    elif (features.is_contiguous(memory_format=torch.channels_last) and C % 4 == 0 and path not in (PATH_DIRECT, PATH_FUSED)
+          and code == DTYPE_FP32):
         layout = LAYOUT_NHWC  # consumed in place: a pixel's channels are already contiguous
     else:
         features, layout = features.contiguous(), LAYOUT_NCHW
@@ -271,17 +310,22 @@ def forward(features: torch.Tensor, rois: torch.Tensor, pooled_height: int, pool
     if channels_last_out and (C % 4 != 0 or path in (PATH_DIRECT, PATH_FUSED)):
         raise ValueError("channels_last_out needs C % 4 == 0 and the tiled path")
     with torch.cuda.device_of(features):
-        out = torch.empty((R, C, ph, pw), dtype=torch.float32, device=features.device,
+        out = torch.empty((R, C, ph, pw), dtype=features.dtype, device=features.device,
                           memory_format=torch.channels_last if channels_last_out else torch.contiguous_format)
         if R == 0 or out.numel() == 0:
             return out
         nbytes = 0 if path in (PATH_DIRECT, PATH_FUSED) else _lib.rroi_align_forward_workspace_bytes(B, C, H, W, R, layout)
         ws = _workspace(features.device, nbytes)
-        st = _lib.rroi_align_forward_layout_hip(features.data_ptr(), layout,
-                                                LAYOUT_NHWC if channels_last_out else LAYOUT_NCHW,
-                                                float(spatial_scale), B, R, H, W, C, ph, pw, rois.data_ptr(),
-                                                out.data_ptr(), ws.data_ptr(), nbytes, word, _stream())
-    _check(st, "rroi_align_forward_hip")
+        top_layout = LAYOUT_NHWC if channels_last_out else LAYOUT_NCHW
+        if code == DTYPE_FP32:
+            st = _lib.rroi_align_forward_layout_hip(features.data_ptr(), layout, top_layout,
+                                                    float(spatial_scale), B, R, H, W, C, ph, pw, rois.data_ptr(),
+                                                    out.data_ptr(), ws.data_ptr(), nbytes, word, _stream())
+        else:
+            st = _lib.rroi_align_forward_typed_hip(features.data_ptr(), code, layout, top_layout, float(spatial_scale),
+                                                   B, R, H, W, C, ph, pw, rois.data_ptr(), out.data_ptr(),
+                                                   ws.data_ptr(), nbytes, word, _stream())
+    _check(st, "rroi_align_forward_hip" if code == DTYPE_FP32 else "rroi_align_forward_typed_hip")
     return out
 
 
@@ -289,10 +333,14 @@ def backward(grad_output: torch.Tensor, rois: torch.Tensor, feature_size, spatia
              path: int = PATH_AUTO, channels_last_grad: bool = False, trig: int = TRIG_DOUBLE) -> torch.Tensor:
     """(R,C,PH,PW) -> grad w.r.t. features (B,C,H,W): NCHW contiguous, or (channels_last_grad, for a
     channels_last backbone; needs C % 4 == 0 and the tiled path) in channels_last storage.
-    trig: the recipe the forward of these crops ran with."""
+    trig: the recipe the forward of these crops ran with.
+    grad_output: float32, bfloat16 or float16 -- the gradient has the same dtype (a 16-bit call sums every gradient
+    element in fp32 and rounds it once; a channels_last 16-bit grad_output is made contiguous first; PATH_DIRECT and
+    PATH_TILED_ATOMIC are fp32 only).  rois: float32."""
     word = _path_word(path, trig)
-    _require_cuda_f32(grad_output, "grad_output")
+    _require_cuda_f32(grad_output, "grad_output", _IO_DTYPES)
     _require_cuda_f32(rois, "rois")
+    code = _DTYPES[grad_output.dtype]
     B, C, H, W = (int(v) for v in feature_size)
     if grad_output.dim() != 4 or grad_output.size(1) != C or grad_output.size(0) != rois.size(0):
         raise ValueError("grad_output must be (R,C,PH,PW) matching rois and the feature size")
@@ -302,24 +350,29 @@ def backward(grad_output: torch.Tensor, rois: torch.Tensor, feature_size, spatia
     # the 256 MiB, no relayout pass
     layout = LAYOUT_NCHW
     if (not grad_output.is_contiguous() and grad_output.is_contiguous(memory_format=torch.channels_last)
-            and C % 4 == 0 and path in (PATH_AUTO,) + GATHER_PATHS and R > 0):
+            and C % 4 == 0 and path in (PATH_AUTO,) + GATHER_PATHS and R > 0 and code == DTYPE_FP32):
         layout = LAYOUT_NHWC
     else:
         grad_output = grad_output.contiguous()
     rois = rois.contiguous()
     cl_grad = bool(channels_last_grad) and C % 4 == 0 and path in (PATH_AUTO,) + GATHER_PATHS and R > 0
     with torch.cuda.device_of(grad_output):
-        grad_in = torch.empty((B, C, H, W), dtype=torch.float32, device=grad_output.device,
+        grad_in = torch.empty((B, C, H, W), dtype=grad_output.dtype, device=grad_output.device,
                               memory_format=torch.channels_last if cl_grad else torch.contiguous_format)
         if grad_in.numel() == 0:
             return grad_in
         nbytes = 0 if path == PATH_DIRECT else _lib.rroi_align_backward_workspace_bytes(B, C, H, W, R, ph, pw)
         ws = _workspace(grad_output.device, nbytes)
-        st = _lib.rroi_align_backward_layout_hip(grad_output.data_ptr(), layout,
-                                                 LAYOUT_NHWC if cl_grad else LAYOUT_NCHW, float(spatial_scale),
-                                                 B, R, H, W, C, ph, pw, rois.data_ptr(), grad_in.data_ptr(),
-                                                 ws.data_ptr(), nbytes, word, _stream())
-    _check(st, "rroi_align_backward_hip")
+        bottom_layout = LAYOUT_NHWC if cl_grad else LAYOUT_NCHW
+        if code == DTYPE_FP32:
+            st = _lib.rroi_align_backward_layout_hip(grad_output.data_ptr(), layout, bottom_layout, float(spatial_scale),
+                                                     B, R, H, W, C, ph, pw, rois.data_ptr(), grad_in.data_ptr(),
+                                                     ws.data_ptr(), nbytes, word, _stream())
+        else:
+            st = _lib.rroi_align_backward_typed_hip(grad_output.data_ptr(), code, layout, bottom_layout,
+                                                    float(spatial_scale), B, R, H, W, C, ph, pw, rois.data_ptr(),
+                                                    grad_in.data_ptr(), ws.data_ptr(), nbytes, word, _stream())
+    _check(st, "rroi_align_backward_hip" if code == DTYPE_FP32 else "rroi_align_backward_typed_hip")
     return grad_in
 
 

@@ -18,7 +18,9 @@ from .._ext import rroi_align
 class _RRoiAlignOp(Function):
     # Under torch.autocast the op stays what the reference is -- an fp32 operator: half / bfloat16 features are
     # cast up on the way in (the reference's THCudaTensor signature would reject them), the crops come out fp32 and
-    # autograd casts the feature gradient back to the features' dtype.
+    # autograd casts the feature gradient back to the features' dtype.  Outside autocast (a model moved to bfloat16 or
+    # float16) custom_fwd casts nothing: the op runs natively in the features' dtype (0.10.0) -- crops and feature
+    # gradient in that dtype, computed in fp32 and rounded once per element; rois stay float32.
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, features, rois, pooled_height, pooled_width, spatial_scale, channels_last_out=False,

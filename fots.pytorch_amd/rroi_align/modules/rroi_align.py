@@ -9,6 +9,13 @@ the crops in channels_last storage (same values) for a recognition head that run
 the gradient that comes back in channels_last is consumed in place as well.  ``trig=1`` evaluates the
 angle's cosine / sine with the device library's fp32 functions (what the reference's sources do when built
 for this GPU) instead of the oracle's correctly rounded recipe; forward and backward of a call use the same.
+
+Precision: float32 features give float32 crops.  bfloat16 / float16 features (a model moved to that dtype, outside
+torch.autocast) run natively: the crops and the feature gradient come back in the features' dtype, each element
+computed in fp32 and rounded once -- the crops are bit for bit the fp32 op's crops of the widened features, rounded.
+Under torch.autocast nothing changes: the features are cast up and the crops are float32.  ``rois`` are float32 always.
+Channels_last 16-bit features and gradients are made contiguous before the call (no zero-copy form); channels_last
+crops (``channels_last_out=True``) and a channels_last feature gradient are produced as for float32.
 """
 from torch.nn.modules.module import Module
 

@@ -254,6 +254,45 @@ int rroi_align_backward_plan(int top_diff_layout, int bottom_diff_layout, int ba
                              int width, int channels, int pooled_height, int pooled_width, int path, int caller,
                              rroi_align_plan* plan);
 
+/* Half-precision I/O (0.10.0).  The element type of the caller's map and crops (forward) or top_diff and bottom_diff
+ * (backward); `rois` are fp32 in every case (they carry the geometry).  Arithmetic: every element is widened exactly
+ * to fp32, the geometry, taps and blend run unchanged in fp32 (the recipe above, `path`'s trig bit included), and
+ * every result is rounded ONCE to the tensor's type, to nearest even (NaN stays NaN, -0.0 stays -0.0): a half forward
+ * equals the fp32 forward of the widened map rounded to the type, bit for bit.  The backward sums every gradient
+ * element in fp32 and rounds it once (no 16-bit atomics); bottom_diff is written, never added to.
+ * What a 16-bit call may run:
+ *   forward   features NCHW (no zero copy: repack channels-last features first), crops NCHW or NHWC; path AUTO,
+ *             DIRECT or TILED -- RROI_PATH_FUSED is refused; native entry point only (the launchers of section 1 are
+ *             fp32).  The two-launch path relays the map out to the same fp32 chunk-major copy as an fp32 call.
+ *   backward  top_diff NCHW (repack a channels-last gradient first), bottom_diff NCHW or NHWC; path AUTO, TILED,
+ *             TILED_LISTS, TILED_BUCKETS or TILED_INKERNEL -- RROI_PATH_DIRECT and RROI_PATH_TILED_ATOMIC (fp32
+ *             atomics) are refused, and AUTO takes the gather TILED would take where an fp32 call would run DIRECT.
+ *             A 16-bit backward is refused (0) where the gather's 32-bit indices do not hold: 4 x R x PH x PW >= 2^32
+ *             pair slots, PH x PW x ceil(C / 32) x 128 >= 2^32 bytes of one ROI's gradient copy, or B x ceil(H / 4) x
+ *             ceil(W / 8) x 32 >= 2^26 map keys (about 64 M map pixels) -- far beyond a training step; an fp32 call
+ *             falls back to the atomic scatter there.
+ * Workspace: a typed call needs no more than rroi_align_forward_workspace_bytes / rroi_align_backward_workspace_bytes
+ * report for the same shape (the workspace is the same fp32 workspace whatever the dtype).
+ * For RROI_DTYPE_FP32 the typed functions are the untyped ones: same plans, same kernels, same results. */
+#define RROI_DTYPE_FP32 0
+#define RROI_DTYPE_BF16 1
+#define RROI_DTYPE_FP16 2
+int rroi_align_forward_typed_hip(const void* features, int dtype, int feature_layout, int top_layout, float spatial_scale,
+                                 int batch_size, int num_rois, int height, int width, int channels, int pooled_height,
+                                 int pooled_width, const float* rois, void* top_data, void* workspace,
+                                 size_t workspace_bytes, int path, void* stream);
+int rroi_align_backward_typed_hip(const void* top_diff, int dtype, int top_diff_layout, int bottom_diff_layout,
+                                  float spatial_scale, int batch_size, int num_rois, int height, int width, int channels,
+                                  int pooled_height, int pooled_width, const float* rois, void* bottom_diff,
+                                  void* workspace, size_t workspace_bytes, int path, void* stream);
+/* The plan queries of a typed call (host only, as above).  RROI_DTYPE_FP32: exactly the untyped query's plan. */
+int rroi_align_forward_plan_typed(int dtype, int feature_layout, int top_layout, int batch_size, int num_rois, int height,
+                                  int width, int channels, int pooled_height, int pooled_width, int path, int caller,
+                                  rroi_align_plan* plan);
+int rroi_align_backward_plan_typed(int dtype, int top_diff_layout, int bottom_diff_layout, int batch_size, int num_rois,
+                                   int height, int width, int channels, int pooled_height, int pooled_width, int path,
+                                   int caller, rroi_align_plan* plan);
+
 /* ------------------------------------------------------------------------- *
  * 3. The callers' ROI construction, on the device.
  *    quads (n, 8) fp32 [x0,y0,x1,y1,x2,y2,x3,y3] -> rois (n, 6) fp32 rows for the
@@ -349,7 +388,7 @@ int rroi_align_write_probe_hip(float* out, size_t num_floats, void* stream);
 int rroi_align_set_trig_recipe_hip(int recipe);
 int rroi_align_get_trig_recipe_hip(void);
 
-/* Identification: "rroi_align_hip <version> gfx950" (0.7.0: per-call trig recipe, device-wide setter removed; 0.8.0: launcher scratch reused within a capture, table of 64, stats; 0.9.0: plan query). */
+/* Identification: "rroi_align_hip <version> gfx950" (0.7.0: per-call trig recipe, device-wide setter removed; 0.8.0: launcher scratch reused within a capture, table of 64, stats; 0.9.0: plan query; 0.10.0: bfloat16 / float16 tensors). */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
