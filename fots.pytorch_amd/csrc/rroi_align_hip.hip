@@ -554,7 +554,8 @@ FwdDispatch plan_forward(int feature_layout, int top_layout, int batch_size, int
     if (half && (caller != RROI_CALLER_NATIVE || feature_layout != RROI_LAYOUT_NCHW ||
                  (path & 0xff) == RROI_PATH_FUSED))
         return P;
-    if (path & ~(0xff | RROI_PATH_TRIG_FP32)) return P;   // unknown flag bits
+    // unknown flag bits (RROI_PATH_DETERMINISTIC among them: a backward flag -- the forward is deterministic as it is)
+    if (path & ~(0xff | RROI_PATH_TRIG_FP32)) return P;
     P.trig = (path & RROI_PATH_TRIG_FP32) ? RROI_TRIG_FP32 : RROI_TRIG_DOUBLE;
     path &= 0xff;
     P.launcher = caller != RROI_CALLER_NATIVE;
@@ -675,6 +676,8 @@ static inline bool gather_choice_is_open(int path)
 // dtype (0.10.0): the element type of top_diff and bottom_diff.  A 16-bit call is native-only, reads an
 // NCHW top_diff, and runs one of the three gathers (never the fp32-atomic DIRECT / ATOMIC forms): AUTO takes the gather
 // TILED would take, and a problem no gather can index is refused.
+// RROI_PATH_DETERMINISTIC: native AUTO calls only; every R >= 1 runs ORDERED -- the exact lists, sorted,
+// and the in-order fp64 gather, written in place in either layout -- where the gather can index the problem.
 BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch_size, int num_rois, int height, int width,
                           int channels, int pooled_height, int pooled_width, int path, int caller, int dtype = RROI_DTYPE_FP32)
 {
@@ -684,7 +687,9 @@ BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch
     if (half && (caller != RROI_CALLER_NATIVE || top_diff_layout != RROI_LAYOUT_NCHW ||
                  (path & 0xff) == RROI_PATH_DIRECT || (path & 0xff) == RROI_PATH_TILED_ATOMIC))
         return P;
-    if (path & ~(0xff | RROI_PATH_TRIG_FP32)) return P;   // unknown flag bits
+    if (path & ~(0xff | RROI_PATH_TRIG_FP32 | RROI_PATH_DETERMINISTIC)) return P;   // unknown flag bits
+    const bool ordered = (path & RROI_PATH_DETERMINISTIC) != 0;
+    if (ordered && (caller != RROI_CALLER_NATIVE || (path & 0xff) != RROI_PATH_AUTO)) return P;
     P.trig = (path & RROI_PATH_TRIG_FP32) ? RROI_TRIG_FP32 : RROI_TRIG_DOUBLE;
     path &= 0xff;
     if (caller == RROI_CALLER_LAUNCHER) {
@@ -728,7 +733,7 @@ BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch
     const int NB = pooled_height * pooled_width;
     const size_t HW = (size_t)height * width;
     const bool accumulate = P.accumulate;
-    const bool tiled = half || td_nhwc || bd_nhwc || (path == RROI_PATH_AUTO
+    const bool tiled = ordered || half || td_nhwc || bd_nhwc || (path == RROI_PATH_AUTO
                                        ? pick_tiled_bwd(batch_size, channels, height, width, num_rois, NB)
                                        : path != RROI_PATH_DIRECT);
     if (accumulate && (!tiled || bd_nhwc)) return P;
@@ -746,6 +751,7 @@ BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch
     P.ws = ws;
     if ((td_nhwc || bd_nhwc) && (!ws.gather_ok || (size_t)num_rois * NB >= (1ull << 32))) return P;
     if (half && !ws.gather_ok) return P;   // (the atomic scatter, an fp32 call's fallback, has no 16-bit form)
+    if (ordered && !ws.gather_ok) return P;   // (... nor an ordered one)
     const bool gather = path != RROI_PATH_TILED_ATOMIC && ws.gather_ok;
     // Two gathers.  K3t builds the pixel lists inside the gather kernel (rroi_backward_tile_kernels.h), K3g
     // with count / scan / fill launches in HBM.  Measured (tools/crossover.py, MI355X, us per call,
@@ -776,9 +782,9 @@ BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch
     // of 128: 74 / 89 / 164) and lose where most of a list lives in the chains (512 per pixel in buckets of 128:
     // 200 / 128 / 318): the bucket grows with the density as far as carve_bwd's cap lets it, bucket_pref says if
     // that was far enough.
-    const bool buckets = gather && ws.bucket_ok && gather_choice_is_open(path) &&
+    const bool buckets = !ordered && gather && ws.bucket_ok && gather_choice_is_open(path) &&
                          (path == RROI_PATH_TILED_BUCKETS || (ws.bucket_pref && g_tune.bwd_buckets));
-    const bool lists = buckets || path == RROI_PATH_TILED_LISTS || !inkernel_ok ||
+    const bool lists = ordered || buckets || path == RROI_PATH_TILED_LISTS || !inkernel_ok ||
                        (path != RROI_PATH_TILED_INKERNEL && !prefer_inkernel);
     P.tt = ceil_div(NB, kRelayoutPx);
     if (gather && !lists) {
@@ -803,7 +809,7 @@ BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch
         P.dest = bd_nhwc ? RROI_PLAN_DST_NHWC : RROI_PLAN_DST_CHUNK_MAJOR;
     } else if (gather) {
         // (1) pixel -> (bin, weight) lists: count, scan, fill -- or buckets in one pass
-        P.family = buckets ? RROI_PLAN_BWD_BUCKETS : RROI_PLAN_BWD_LISTS;
+        P.family = ordered ? RROI_PLAN_BWD_ORDERED : buckets ? RROI_PLAN_BWD_BUCKETS : RROI_PLAN_BWD_LISTS;
         // few scan blocks: every consumer block prefix-sums their totals itself (no second scan launch)
         P.raw_bsum = ws.scan_blocks <= kInlineScanBlocks ? 1 : 0;
         // one pair block per CU, looping over the bins: the pair passes need outstanding atomics,
@@ -849,8 +855,9 @@ BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch
         // scratch form beyond 16 bins per pixel.  C <= 128 gains at every density measured: R = 512, C = 64 / 128
         // 76.0 -> 71.9 / 76.5 -> 71.2, R = 16...32 36.8 -> 29.0 / 24.3 -> 17.9 (the relayout launch was a fifth of
         // those calls), 84 bins per pixel 159 -> 153.
-        const bool nchw_direct = !bd_nhwc && g_tune.bwd_nchw_direct != 0 &&
-                                 (nchunks <= 4 || (double)num_rois * NB <= (double)g_tune.bwd_nchw_direct * (double)batch_size * HW);
+        // (ORDERED: always in place -- its gather has no chunk-major form)
+        const bool nchw_direct = !bd_nhwc && (ordered || (g_tune.bwd_nchw_direct != 0 &&
+                                 (nchunks <= 4 || (double)num_rois * NB <= (double)g_tune.bwd_nchw_direct * (double)batch_size * HW)));
         unsigned gy = 1;
         if (nchw_direct && sub_shift == 6) {
             sub_shift = 5;
@@ -1387,6 +1394,7 @@ static int launch_backward(const BwdDispatch& P, const T* top_diff, float spatia
     case RROI_PLAN_BWD_INKERNEL:
     case RROI_PLAN_BWD_LISTS:
     case RROI_PLAN_BWD_BUCKETS:
+    case RROI_PLAN_BWD_ORDERED:
         break;
     default:   // (the literal kernel is the launcher's own)
         return 0;
@@ -1403,7 +1411,8 @@ static int launch_backward(const BwdDispatch& P, const T* top_diff, float spatia
     const int ptiles = ceil_div((long)HW, kRelayoutPx);
     const bool gather = P.family != RROI_PLAN_BWD_ATOMIC;
     const bool buckets = P.family == RROI_PLAN_BWD_BUCKETS;
-    const bool lists = buckets || P.family == RROI_PLAN_BWD_LISTS;
+    const bool ordered = P.family == RROI_PLAN_BWD_ORDERED;
+    const bool lists = buckets || ordered || P.family == RROI_PLAN_BWD_LISTS;
     const BucketLists BL = {ws.kshift, reinterpret_cast<int*>(ws.off), ws.bsum, ws.ov};
     {
         // affine table; the list passes' pixel counters (K3g) are cleared by the same launch
@@ -1524,6 +1533,24 @@ static int launch_backward(const BwdDispatch& P, const T* top_diff, float spatia
         if (st != 1) return st;
         // (3) gather: one thread group per key, no grid-stride
         const unsigned sub_shift = P.sub_shift, tile_run = P.tile_run;
+        if (ordered) {
+            // (2b) every list in bin order: the short ones in registers, the rest queued in the counters (which the
+            // fill left at zero) for one workgroup each; then the in-order fp64 gather, in place
+            unsigned* const queue = reinterpret_cast<unsigned*>(ws.cnt);
+            hipLaunchKernelGGL(rroi_bwd_sort_lists_kernel, dim3(ceil_div((long)KL.keys, 4L)), dim3(256), 0, stream,
+                               ws.off, ws.bsum, ws.pairs, KL.keys, ws.scan_blocks, raw_bsum, queue);
+            hipLaunchKernelGGL(rroi_bwd_sort_queue_kernel, dim3(num_cus() * 4), dim3(kSortQueueThreads), 0, stream,
+                               ws.off, ws.bsum, ws.pairs, queue, ws.scan_blocks, raw_bsum);
+#define RROI_LAUNCH_OG(DSTK)                                                                                   \
+    hipLaunchKernelGGL((rroi_bwd_ordered_gather_kernel<DSTK, T>), P.grid, dim3(256), 0, stream, srcT, ws.off,   \
+                       ws.bsum, ws.pairs, bottom_diff, channels, height, width, nchunks, chunk_stride,            \
+                       line_stride, sub_shift, KL, make_fastdiv(KL.Ht * KL.Wt), make_fastdiv(KL.Wt),              \
+                       ws.scan_blocks, raw_bsum, tile_run)
+            if (P.dest == RROI_PLAN_DST_NHWC) RROI_LAUNCH_OG(kDstNhwc);
+            else RROI_LAUNCH_OG(kDstNchw);
+#undef RROI_LAUNCH_OG
+            return launch_status();
+        }
         // the lists: count / scan / fill segments (`off` = scanned offsets) or buckets (`off` = the counters)
         const unsigned* loff = buckets ? reinterpret_cast<const unsigned*>(ws.cnt) : ws.off;
 #define RROI_LAUNCH_G(DSTK, BUCK, DST)                                                                        \
@@ -1763,6 +1790,8 @@ static int launcher_trig()
 // their scratch from the library's per-(device, stream) buffers (launcher_scratch above: grown on
 // demand, reused by later calls, pinned once a graph has captured them; no synchronisation).
 // Small problems keep the one-kernel direct paths (no scratch).
+int rroi_align_launcher_trig_recipe(void) { return launcher_trig(); }
+
 int RROIAlignForwardLaucher(const float* bottom_data, const float spatial_scale,
                             const int num_rois, const int height, const int width,
                             const int channels, const int pooled_height, const int pooled_width,
@@ -1883,7 +1912,8 @@ int rroi_align_backward_plan_typed(int dtype, int top_diff_layout, int bottom_di
     const BwdDispatch P = plan_backward(top_diff_layout, bottom_diff_layout, batch_size, num_rois, height, width, channels,
                                         pooled_height, pooled_width, path, caller, dtype);
     if (!P.status) return 0;
-    const bool lists = P.family == RROI_PLAN_BWD_LISTS || P.family == RROI_PLAN_BWD_BUCKETS;
+    const bool lists = P.family == RROI_PLAN_BWD_LISTS || P.family == RROI_PLAN_BWD_BUCKETS ||
+                       P.family == RROI_PLAN_BWD_ORDERED;
     fill_plan(plan, P.family, -1, 0, P.family == RROI_PLAN_BWD_ATOMIC ? P.ntiles : 0,
               P.family == RROI_PLAN_NONE ? dim3(0, 0, 0) : P.grid, P.td_nhwc && P.family != RROI_PLAN_NONE, false, P.nk,
               P.family == RROI_PLAN_BWD_BUCKETS ? (int)P.ws.kshift : 0, lists ? P.raw_bsum : -1, lists ? (int)P.gy : 0,

@@ -1,4 +1,4 @@
-// rroi_backward_kernels.h -- backward: gather formulation (K3g), atomic scatter (K3), relayout back to NCHW, direct and literal kernels
+// rroi_backward_kernels.h -- backward: gather formulation (K3g), its ORDERED form, atomic scatter (K3), relayout back to NCHW, direct and literal kernels
 // Part of the single translation unit rroi_align_hip.hip (included inside its anonymous
 // namespace, in this order: rroi_device_common.h, rroi_forward_kernels.h,
 // rroi_backward_kernels.h, rroi_callers_kernels.h); not a standalone header.
@@ -552,6 +552,230 @@ __global__ __launch_bounds__(256) void rroi_bwd_gather_kernel(
                           ? gcm + (((size_t)b * height + y) * width + x) * (size_t)C + k * kChunk + quad * 4u
                           : gcm + (((size_t)b * nchunks + k) * slice_px + (size_t)y * pitch + x) * kChunk + quad * 4u;
             store4(dst, acc);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------
+// ORDERED (RROI_PATH_DETERMINISTIC): the deterministic backward.  The count / scan / fill passes of the
+// lists above build the same per-pixel segments on every run -- the counts do not depend on the order the atomics
+// come in, so neither do the offsets -- but the ORDER inside a segment does.  A sort pass puts every segment in
+// ascending bin-line order (n * NB + j: ROI, then pooled row, then column -- unique within a list, a bin emits one
+// pair per distinct pixel), and the gather below walks it strictly in that order, adding the fp32 products in double:
+// rroi_oracle_backward's sum, term for term.
+// Sort: up to 64 entries (configs[2]: 17 on average) one wave per list, a rank sort in registers, in
+// rroi_bwd_sort_lists_kernel -- which holds no LDS beyond the scan blocks' prefix, so nothing but registers limits how
+// many of its waves a CU keeps.  Longer lists (hundreds: the overlap generator; thousands: many copies of one ROI) are
+// queued for rroi_bwd_sort_queue_kernel, one workgroup per list: a bitonic sort in LDS up to kSortLdsCap entries, in
+// place in global memory beyond.  The queue lives in the pixel counters, which the fill pass has counted back down to
+// zero: [0] = length, [1 ..) = keys -- at most keys - 1 of them, because key 0 (pixel (0, 0) of image 0) fails every
+// bound of kernel.cu:267-274.
+// ------------------------------------------------------------------------------------
+constexpr unsigned kSortRegCap = 64;       // entries of a list one wave rank-sorts in registers
+constexpr unsigned kSortLdsCap = 4096;     // entries of a queued list sorted in LDS (32 KB)
+constexpr unsigned kSortQueueThreads = 256;
+
+__device__ __forceinline__ unsigned ceil_pow2(unsigned m)
+{
+    return m <= 1u ? 1u : 1u << (32 - __builtin_clz(m - 1u));
+}
+
+__global__ __launch_bounds__(256) void rroi_bwd_sort_lists_kernel(const unsigned* __restrict__ off,
+                                                                  const unsigned* __restrict__ bsum,
+                                                                  uint2* __restrict__ pairs, unsigned keys,
+                                                                  unsigned scan_blocks, int raw_bsum,
+                                                                  unsigned* __restrict__ queue)
+{
+    __shared__ unsigned bs_lds[kInlineScanBlocks];
+    bsum = block_prefix(bsum, scan_blocks, raw_bsum != 0, bs_lds);   // (the block's only barrier)
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned key = blockIdx.x * 4u + wave;
+    if (key >= keys) return;
+    const unsigned beg = list_offset(off, bsum, key), end = list_offset(off, bsum, key + 1u);
+    const unsigned m = end - beg;
+    if (m <= 1u) return;
+    if (m > kSortRegCap) {
+        if (lane == 0u) {
+            const unsigned q = atomicAdd(queue, 1u);   // (the queue's order only decides which workgroup sorts a list)
+            queue[1u + q] = key;
+        }
+        return;
+    }
+    // rank = entries with a smaller bin line (ties, which a list cannot hold, by lane); m is wave-uniform, so entry j
+    // comes over as a scalar (v_readlane), not through an LDS permute
+    const uint2 r = lane < m ? pairs[beg + lane] : make_uint2(0xffffffffu, 0u);
+    unsigned rank = 0u;
+    for (unsigned j = 0; j < m; ++j) {
+        const unsigned o = (unsigned)__builtin_amdgcn_readlane((int)r.x, (int)j);
+        rank += (o < r.x || (o == r.x && j < lane)) ? 1u : 0u;
+    }
+    if (lane < m) pairs[beg + rank] = r;
+}
+
+// The queued lists, one workgroup per list.  The bitonic network whose comparators all point up (the first step of
+// every merge compares mirrored positions), so the virtual padding beyond the list never moves: in LDS when the list
+// fits, in place in global memory beyond (workgroup barriers between the steps).  The queue's length is read first:
+// with no queued list (the usual case) every workgroup leaves at once.
+__global__ __launch_bounds__(kSortQueueThreads) void rroi_bwd_sort_queue_kernel(const unsigned* __restrict__ off,
+                                                                               const unsigned* __restrict__ bsum,
+                                                                               uint2* __restrict__ pairs,
+                                                                               const unsigned* __restrict__ queue,
+                                                                               unsigned scan_blocks, int raw_bsum)
+{
+    const unsigned nq = queue[0];
+    if (blockIdx.x >= nq) return;   // (uniform over the workgroup)
+    __shared__ unsigned bs_lds[kInlineScanBlocks];
+    __shared__ uint2 s[kSortLdsCap];
+    bsum = block_prefix(bsum, scan_blocks, raw_bsum != 0, bs_lds);
+    for (unsigned l = blockIdx.x; l < nq; l += gridDim.x) {
+        const unsigned key = queue[1u + l];
+        const unsigned beg = list_offset(off, bsum, key), m = list_offset(off, bsum, key + 1u) - beg;
+        const unsigned M = ceil_pow2(m);
+        const bool lds = M <= kSortLdsCap;
+        uint2* const g = pairs + beg;
+        if (lds) {
+            for (unsigned i = threadIdx.x; i < m; i += kSortQueueThreads) s[i] = g[i];
+            __syncthreads();
+        }
+        uint2* const a = lds ? s : g;
+        for (unsigned k = 2u; k <= M; k <<= 1) {
+            for (unsigned j = k >> 1; j > 0u; j >>= 1) {
+                for (unsigned t = threadIdx.x; t < M / 2u; t += kSortQueueThreads) {
+                    const unsigned lo = ((t & ~(j - 1u)) << 1) | (t & (j - 1u));
+                    const unsigned hi = j == (k >> 1) ? lo ^ (k - 1u) : lo + j;
+                    if (hi < m) {
+                        const uint2 x = a[lo], y = a[hi];
+                        if (x.x > y.x) {
+                            a[lo] = y;
+                            a[hi] = x;
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        if (lds) {
+            for (unsigned i = threadIdx.x; i < m; i += kSortQueueThreads) g[i] = s[i];
+            __syncthreads();   // (the next list reuses the tile)
+        }
+    }
+}
+
+// The ORDERED gather: rroi_bwd_gather_kernel's thread -> (pixel, channel quad) map, grid and NCHW / NHWC stores, over
+// the sorted lists, with every entry added in list order as acc += (double)(w * g) -- the product in fp32, as the
+// reference forms it, then widened exactly -- and the sum rounded once: (float)acc, and from there to TO.  As in the
+// gather, the fast walk leaves out the reference's extra 0 * g of an aliased tap: with every g finite those terms add
+// +-0 to a sum that started at +0.0 and can never be -0.0, i.e. nothing; where a sum is not finite (a g is not) the
+// wave walks its lists again with them.
+template <int DST, class TO = float>
+__global__ __launch_bounds__(256) void rroi_bwd_ordered_gather_kernel(
+    const float* __restrict__ tdT, const unsigned* __restrict__ off, const unsigned* __restrict__ bsum,
+    const uint2* __restrict__ pairs, TO* __restrict__ out, int C, int height, int width, int nchunks,
+    unsigned chunk_stride, unsigned line_stride, unsigned sub_shift, KeyLayout L, FastDiv div_bt, FastDiv div_wt,
+    unsigned scan_blocks, int raw_bsum, unsigned tile_run)
+{
+    static_assert(DST == kDstNchw || DST == kDstNhwc, "ORDERED writes the caller's gradient in place");
+    typedef double v4d __attribute__((ext_vector_type(4)));
+    constexpr bool TO_NCHW = DST == kDstNchw;
+    constexpr unsigned THREADS = 256u, kLogThreads = 8u;
+    __shared__ unsigned bs_lds[kInlineScanBlocks];
+    __shared__ float xpose[TO_NCHW ? THREADS * 4 : 4];
+    bsum = block_prefix(bsum, scan_blocks, raw_bsum != 0, bs_lds);  // before any thread leaves
+    const unsigned gshift = sub_shift + 5u - kLogThreads;
+    const unsigned bq = blockIdx.x >> 3, xcd = blockIdx.x & 7u;
+    const unsigned tq = bq >> gshift;
+    const unsigned tile = ((tq >> tile_run) << (3u + tile_run)) + (xcd << tile_run) + (tq & ((1u << tile_run) - 1u));
+    const unsigned wg = (tile << gshift) + (bq & ((1u << gshift) - 1u));
+    const unsigned tid = wg * THREADS + threadIdx.x;
+    const unsigned sub = 1u << sub_shift;
+    const unsigned sl = tid & (sub - 1u);
+    const unsigned key = tid >> sub_shift;
+    bool live = key < L.keys;
+    const unsigned blk = (live ? key : 0u) >> 5, in = key & 31u;
+    const unsigned b = fdiv(blk, div_bt);
+    const unsigned r = blk - b * (L.Ht * L.Wt);
+    const unsigned by = fdiv(r, div_wt);
+    const unsigned y = by * 4u + (in >> 3), x = (r - by * L.Wt) * 8u + (in & 7u);
+    live = live && y < (unsigned)height && x < (unsigned)width;
+    if (!TO_NCHW && !live) return;
+    unsigned beg = 0u, end = 0u;
+    if (live) {
+        beg = list_offset(off, bsum, key);
+        end = list_offset(off, bsum, key + 1u);
+    }
+    const unsigned quad = sl & 7u;
+    const v4f z4 = {0.f, 0.f, 0.f, 0.f};
+    constexpr int kDepth = 8;
+    const unsigned kstep = gridDim.y * (sub >> 3);
+    for (unsigned k0 = blockIdx.y * (sub >> 3); k0 < (unsigned)nchunks; k0 += kstep) {
+        const unsigned k = k0 + (sl >> 3);
+        const bool c_ok = k < (unsigned)nchunks && k * kChunk + quad * 4u < (unsigned)C;
+        const float* src = tdT + (size_t)k * chunk_stride + quad * 4u;
+        const unsigned group_base = (threadIdx.x & 63u) & ~(sub - 1u);
+        auto walk = [&](auto exact_tag) {
+            constexpr bool EXACT = decltype(exact_tag)::value;
+            v4d acc = {0.0, 0.0, 0.0, 0.0};
+            for (unsigned base = beg; base < end; base += sub) {
+                const unsigned m = min(sub, end - base);
+                const uint2 rec = sl < m ? pairs[base + sl] : make_uint2(0u, 0u);
+                for (unsigned j = 0; j < m; j += kDepth) {
+                    v4f g[kDepth];
+                    unsigned wb[kDepth];
+#pragma unroll
+                    for (int d = 0; d < kDepth; ++d) {
+                        const int from = (int)(group_base + j + d);
+                        const unsigned line = (unsigned)__shfl((int)rec.x, from, kWave);
+                        wb[d] = (unsigned)__shfl((int)rec.y, from, kWave);
+                        g[d] = (c_ok && j + d < m) ? *reinterpret_cast<const v4f*>(src + (size_t)line * line_stride) : z4;
+                    }
+#pragma unroll
+                    for (int d = 0; d < kDepth; ++d) {
+                        if (j + d < m) {
+                            const v4f p = g[d] * as_f(wb[d] & 0x7fffffffu);   // kernel.cu:260-263, in fp32
+                            acc += __builtin_convertvector(p, v4d);
+                            if (EXACT && (wb[d] & 0x80000000u)) acc += __builtin_convertvector(g[d] * 0.0f, v4d);
+                        }
+                    }
+                }
+            }
+            return acc;
+        };
+        v4d acc = walk(std::false_type{});
+        {
+            constexpr double kMax = __DBL_MAX__;
+            const bool bad = !(fabs(acc.x) <= kMax) || !(fabs(acc.y) <= kMax) || !(fabs(acc.z) <= kMax) ||
+                             !(fabs(acc.w) <= kMax);
+            if (__ballot(bad)) acc = walk(std::true_type{});
+        }
+        const v4f res = __builtin_convertvector(acc, v4f);
+        if (TO_NCHW) {
+            // the gather's transpose through LDS: whole 32-byte sectors of a map row per channel
+            *reinterpret_cast<v4f*>(xpose + threadIdx.x * 4u) = res;
+            __syncthreads();
+            const unsigned t = threadIdx.x, cp = sub * 4u;
+            const unsigned c = (t >> 1) & (cp - 1u), row = t >> (sub_shift + 3u), pw0 = row * 8u + (t & 1u) * 4u;
+            const float* tr = xpose + pw0 * cp + c;
+            const v4f v = {tr[0], tr[cp], tr[2u * cp], tr[3u * cp]};
+            const unsigned key0 = (wg * THREADS) >> sub_shift;
+            const unsigned in0 = (key0 & 31u) + pw0;
+            const unsigned blk0 = (key0 < L.keys ? key0 : 0u) >> 5;
+            const unsigned b0 = fdiv(blk0, div_bt), r0 = blk0 - b0 * (L.Ht * L.Wt), by0 = fdiv(r0, div_wt);
+            const unsigned y0 = by0 * 4u + (in0 >> 3), x0 = (r0 - by0 * L.Wt) * 8u + (in0 & 7u);
+            const unsigned cg = k0 * kChunk + c;
+            if (key0 < L.keys && cg < (unsigned)C && y0 < (unsigned)height && x0 < (unsigned)width) {
+                TO* o = out + (((size_t)b0 * C + cg) * height + y0) * (size_t)width + x0;
+                if ((width & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & (4 * sizeof(TO) - 1)) == 0) {
+                    store4(o, v);
+                } else {
+                    const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (x0 + j < (unsigned)width) o[j] = from_f32<TO>(e[j]);
+                }
+            }
+            if (k0 + kstep < (unsigned)nchunks) __syncthreads();   // the next pass reuses the tile
+        } else if (c_ok) {
+            store4(out + (((size_t)b * height + y) * width + x) * (size_t)C + k * kChunk + quad * 4u, res);
         }
     }
 }

@@ -36,6 +36,7 @@ CALLER_NATIVE, CALLER_LAUNCHER, CALLER_LAUNCHER_CON_IDX = 0, 1, 2
 PLAN_NONE = 0
 PLAN_FWD_DIRECT_K2P, PLAN_FWD_DIRECT_THREAD, PLAN_FWD_FUSED_STRIDED, PLAN_FWD_FUSED_SHIFT, PLAN_FWD_TWO_LAUNCH = 1, 2, 3, 4, 5
 PLAN_BWD_DIRECT, PLAN_BWD_ATOMIC, PLAN_BWD_INKERNEL, PLAN_BWD_LISTS, PLAN_BWD_BUCKETS, PLAN_BWD_LITERAL = 11, 12, 13, 14, 15, 16
+PLAN_BWD_ORDERED = 17  # the deterministic backward (PATH_DETERMINISTIC): sorted exact lists, in-order fp64 gather
 PLAN_KERNEL_STRIDED, PLAN_KERNEL_CHANNELS_LAST, PLAN_KERNEL_SHIFT, PLAN_KERNEL_STRIDED_MERGE, PLAN_KERNEL_SHIFT_LINES = 0, 1, 2, 3, 4
 PLAN_DST_NONE, PLAN_DST_CHUNK_MAJOR, PLAN_DST_NCHW, PLAN_DST_NCHW_ADD, PLAN_DST_NHWC = 0, 1, 2, 3, 4
 
@@ -132,6 +133,7 @@ EXPORTS = (
     "rroi_align_forward_plan", "rroi_align_backward_plan",
     "rroi_align_forward_typed_hip", "rroi_align_backward_typed_hip",
     "rroi_align_forward_plan_typed", "rroi_align_backward_plan_typed",
+    "rroi_align_launcher_trig_recipe",
 )
 
 # What a call launches (rroi_align_forward_plan / rroi_align_backward_plan); the fields of rroi_align_plan.
@@ -169,13 +171,13 @@ def forward_plan(batch_size, channels, height, width, num_rois, pooled_height, p
 
 def backward_plan(batch_size, channels, height, width, num_rois, pooled_height, pooled_width,
                   top_diff_layout=LAYOUT_NCHW, bottom_diff_layout=LAYOUT_NCHW, path=PATH_AUTO, caller=CALLER_NATIVE,
-                  trig=0, dtype=DTYPE_FP32) -> Plan:
+                  trig=0, dtype=DTYPE_FP32, deterministic=False) -> Plan:
     """The plan a backward call with these arguments runs (host only, no GPU needed); ValueError where the call
     would refuse them.  dtype: of grad_output and the gradient (a torch dtype or DTYPE_*; the default is the fp32
-    query)."""
+    query).  deterministic: the query of a call with PATH_DETERMINISTIC (backward(deterministic=True))."""
     code = dtype_code(dtype)
     args = (top_diff_layout, bottom_diff_layout, batch_size, num_rois, height, width, channels, pooled_height,
-            pooled_width, _path_word(path, trig), caller)
+            pooled_width, _path_word(path, trig, deterministic), caller)
     if code == DTYPE_FP32:
         return _plan(_lib.rroi_align_backward_plan, args, "rroi_align_backward_plan")
     return _plan(_lib.rroi_align_backward_plan_typed, (code,) + args, "rroi_align_backward_plan_typed")
@@ -192,12 +194,16 @@ def version() -> str:
 # argument, so two streams may run different recipes at once and either is capturable into a graph.
 TRIG_DOUBLE, TRIG_FP32 = 0, 1
 PATH_TRIG_FP32 = 0x100
+# The deterministic backward: backward(deterministic=True) sets this bit of `path` and runs the ORDERED plan
+# -- every gradient element summed in double in the oracle's order and rounded once, the same bits on every run.  With
+# PATH_AUTO only.  A backward flag: the forward is deterministic as it is, and its entry points refuse the bit.
+PATH_DETERMINISTIC = 0x200
 
 
-def _path_word(path: int, trig: int) -> int:
+def _path_word(path: int, trig: int, deterministic: bool = False) -> int:
     if trig not in (TRIG_DOUBLE, TRIG_FP32):
         raise ValueError(f"trig must be TRIG_DOUBLE (0) or TRIG_FP32 (1), got {trig!r}")
-    return int(path) | (PATH_TRIG_FP32 if trig == TRIG_FP32 else 0)
+    return int(path) | (PATH_TRIG_FP32 if trig == TRIG_FP32 else 0) | (PATH_DETERMINISTIC if deterministic else 0)
 
 
 def _check(status: int, what: str) -> None:
@@ -330,14 +336,17 @@ def forward(features: torch.Tensor, rois: torch.Tensor, pooled_height: int, pool
 
 
 def backward(grad_output: torch.Tensor, rois: torch.Tensor, feature_size, spatial_scale: float,
-             path: int = PATH_AUTO, channels_last_grad: bool = False, trig: int = TRIG_DOUBLE) -> torch.Tensor:
+             path: int = PATH_AUTO, channels_last_grad: bool = False, trig: int = TRIG_DOUBLE,
+             deterministic: bool = False) -> torch.Tensor:
     """(R,C,PH,PW) -> grad w.r.t. features (B,C,H,W): NCHW contiguous, or (channels_last_grad, for a
     channels_last backbone; needs C % 4 == 0 and the tiled path) in channels_last storage.
     trig: the recipe the forward of these crops ran with.
     grad_output: float32, bfloat16 or float16 -- the gradient has the same dtype (a 16-bit call sums every gradient
     element in fp32 and rounds it once; a channels_last 16-bit grad_output is made contiguous first; PATH_DIRECT and
-    PATH_TILED_ATOMIC are fp32 only).  rois: float32."""
-    word = _path_word(path, trig)
+    PATH_TILED_ATOMIC are fp32 only).  rois: float32.
+    deterministic: run the ORDERED plan (PATH_DETERMINISTIC, with path=PATH_AUTO only): the same bits on every run, equal
+    to the oracle's double-precision sum in statement order rounded once (16-bit: that fp32 gradient rounded)."""
+    word = _path_word(path, trig, deterministic)
     _require_cuda_f32(grad_output, "grad_output", _IO_DTYPES)
     _require_cuda_f32(rois, "rois")
     code = _DTYPES[grad_output.dtype]
@@ -501,10 +510,20 @@ def rroi_align_forward_cuda(pooled_height, pooled_width, spatial_scale, features
     return 1
 
 
+def _launcher_trig() -> int:
+    """The recipe the reference-ABI launchers run in this process (the library reads RROI_ALIGN_LAUNCHER_TRIG once per
+    process: asking it keeps the glue's gradient on the recipe of the launcher forward that made the crops)."""
+    return int(_lib.rroi_align_launcher_trig_recipe())
+
+
 def rroi_align_backward_cuda(pooled_height, pooled_width, spatial_scale, top_grad, rois,
                              bottom_grad, idx_x, idx_y) -> int:
     """Reference FFI signature (src/rroi_align_cuda.c:49-87).  ``bottom_grad`` must be
-    zero on entry, as functions/rroi_align.py:35 guarantees in the reference."""
+    zero on entry, as functions/rroi_align.py:35 guarantees in the reference.
+    Under torch.use_deterministic_algorithms(True) the gradient is the ORDERED one (backward(deterministic=True),
+    from the rois -- the same bin centres the forward stored in idx_x / idx_y), computed into a temporary and added
+    to ``bottom_grad`` with one torch add: the same bits on every run.  The C launcher itself
+    (RROIAlignBackwardLaucher) has no `path` word and stays the reference's scatter, whose order is not fixed."""
     for t, name in ((top_grad, "top_grad"), (rois, "rois"), (bottom_grad, "bottom_grad"),
                     (idx_x, "idx_x"), (idx_y, "idx_y")):
         _require_cuda_f32(t, name)
@@ -514,6 +533,10 @@ def rroi_align_backward_cuda(pooled_height, pooled_width, spatial_scale, top_gra
         return 0
     num_rois = rois.size(0)
     B, C, H, W = bottom_grad.shape
+    if torch.are_deterministic_algorithms_enabled():
+        g = backward(top_grad, rois, (B, C, H, W), spatial_scale, trig=_launcher_trig(), deterministic=True)
+        bottom_grad.add_(g)
+        return 1
     with torch.cuda.device_of(top_grad):
         st = _lib.RROIAlignBackwardLaucher(top_grad.data_ptr(), float(spatial_scale), B, num_rois, H,
                                            W, C, int(pooled_height), int(pooled_width),

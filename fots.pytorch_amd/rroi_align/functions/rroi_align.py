@@ -15,6 +15,12 @@ from torch.autograd import Function
 from .._ext import rroi_align
 
 
+def _deterministic(flag):
+    """The backward's choice: ``None`` follows torch.are_deterministic_algorithms_enabled() (read when the backward
+    runs), ``True`` / ``False`` force the ORDERED plan / the default AUTO plan."""
+    return torch.are_deterministic_algorithms_enabled() if flag is None else bool(flag)
+
+
 class _RRoiAlignOp(Function):
     # Under torch.autocast the op stays what the reference is -- an fp32 operator: half / bfloat16 features are
     # cast up on the way in (the reference's THCudaTensor signature would reject them), the crops come out fp32 and
@@ -24,7 +30,7 @@ class _RRoiAlignOp(Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, features, rois, pooled_height, pooled_width, spatial_scale, channels_last_out=False,
-                trig=rroi_align.TRIG_DOUBLE):
+                trig=rroi_align.TRIG_DOUBLE, deterministic=None):
         ctx.pooled_height = pooled_height
         ctx.pooled_width = pooled_width
         ctx.spatial_scale = spatial_scale
@@ -33,6 +39,7 @@ class _RRoiAlignOp(Function):
         ctx.channels_last_grad = (features.dim() == 4 and not features.is_contiguous()
                                   and features.is_contiguous(memory_format=torch.channels_last))
         ctx.trig = trig   # the backward recomputes the bin centres: with the forward's recipe
+        ctx.deterministic = deterministic   # None: torch's flag as it stands when the backward runs
         ctx.save_for_backward(rois)
         return rroi_align.forward(features, rois, pooled_height, pooled_width, spatial_scale,
                                   channels_last_out=channels_last_out, trig=trig)
@@ -45,15 +52,16 @@ class _RRoiAlignOp(Function):
         grad_input = None
         if ctx.needs_input_grad[0]:
             grad_input = rroi_align.backward(grad_output, rois, ctx.feature_size, ctx.spatial_scale,
-                                             channels_last_grad=ctx.channels_last_grad, trig=ctx.trig)
-        return grad_input, None, None, None, None, None, None
+                                             channels_last_grad=ctx.channels_last_grad, trig=ctx.trig,
+                                             deterministic=_deterministic(ctx.deterministic))
+        return grad_input, None, None, None, None, None, None, None
 
 
 class RRoiAlignFunction(object):
     """``RRoiAlignFunction(ph, pw, scale)(features, rois) -> (R, C, ph, pw)``."""
 
     def __init__(self, pooled_height, pooled_width, spatial_scale, channels_last_out=False,
-                 trig=rroi_align.TRIG_DOUBLE):
+                 trig=rroi_align.TRIG_DOUBLE, deterministic=None):
         # extension: the recipe of cos / sin of the ROI angle (kernel.cu:73-74) for this object's calls, forward and
         # backward alike: TRIG_DOUBLE (the oracle's) or TRIG_FP32 (the reference's sources built for this GPU)
         self.trig = int(trig)
@@ -62,6 +70,9 @@ class RRoiAlignFunction(object):
         self.spatial_scale = spatial_scale
         # extension: crops in channels_last storage for a channels_last recognition head
         self.channels_last_out = bool(channels_last_out)
+        # extension: the backward's plan -- None follows torch.use_deterministic_algorithms (read at backward time),
+        # True / False force the ORDERED (deterministic) / the default plan
+        self.deterministic = deterministic
         self.feature_size = None
         self.rois = None
 
@@ -69,7 +80,7 @@ class RRoiAlignFunction(object):
         self.feature_size = features.size()
         self.rois = rois
         return _RRoiAlignOp.apply(features, rois, int(self.pooled_height), int(self.pooled_width),
-                                  float(self.spatial_scale), self.channels_last_out, self.trig)
+                                  float(self.spatial_scale), self.channels_last_out, self.trig, self.deterministic)
 
     # the legacy Function's two methods, callable by hand as in torch 0.4
     def forward(self, features, rois):
@@ -81,5 +92,6 @@ class RRoiAlignFunction(object):
     def backward(self, grad_output):
         assert self.feature_size is not None and grad_output.is_cuda
         grad_input = rroi_align.backward(grad_output, self.rois, self.feature_size,
-                                         float(self.spatial_scale), trig=self.trig)
+                                         float(self.spatial_scale), trig=self.trig,
+                                         deterministic=_deterministic(self.deterministic))
         return grad_input, None

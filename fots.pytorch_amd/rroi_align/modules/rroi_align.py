@@ -9,6 +9,9 @@ the crops in channels_last storage (same values) for a recognition head that run
 the gradient that comes back in channels_last is consumed in place as well.  ``trig=1`` evaluates the
 angle's cosine / sine with the device library's fp32 functions (what the reference's sources do when built
 for this GPU) instead of the oracle's correctly rounded recipe; forward and backward of a call use the same.
+``deterministic`` picks the backward's plan: ``None`` (default) follows ``torch.use_deterministic_algorithms`` as it
+stands when the backward runs -- on: the ORDERED plan, the same gradient bits on every run (the oracle's double sum
+in statement order, rounded once) --, ``True`` / ``False`` force the choice.
 
 Precision: float32 features give float32 crops.  bfloat16 / float16 features (a model moved to that dtype, outside
 torch.autocast) run natively: the crops and the feature gradient come back in the features' dtype, each element
@@ -23,8 +26,10 @@ from ..functions.rroi_align import RRoiAlignFunction
 
 
 class _RRoiAlign(Module):
-    def __init__(self, pooled_height, pooled_width, spatial_scale, channels_last_out=False, trig=0):
+    def __init__(self, pooled_height, pooled_width, spatial_scale, channels_last_out=False, trig=0,
+                 deterministic=None):
         super(_RRoiAlign, self).__init__()
+        self.deterministic = None if deterministic is None else bool(deterministic)
         self.trig = int(trig)   # 0 = TRIG_DOUBLE (default), 1 = TRIG_FP32: per call, see _ext.rroi_align
         self.pooled_width = int(pooled_width)
         self.pooled_height = int(pooled_height)
@@ -33,7 +38,7 @@ class _RRoiAlign(Module):
 
     def forward(self, features, rois):
         return RRoiAlignFunction(self.pooled_height, self.pooled_width, self.spatial_scale,
-                                 self.channels_last_out, self.trig)(features, rois)
+                                 self.channels_last_out, self.trig, self.deterministic)(features, rois)
 
     def extra_repr(self):
         return "pooled_height={}, pooled_width={}, spatial_scale={}".format(

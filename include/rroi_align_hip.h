@@ -130,6 +130,27 @@ int rroi_align_launcher_scratch_stats(int* in_use, int* pinned, int* capacity, u
 #define RROI_PATH_TRIG_FP32 0x100
 #define RROI_TRIG_DOUBLE 0
 #define RROI_TRIG_FP32 1
+/* The recipe the reference-ABI launchers run in this process (RROI_TRIG_DOUBLE / RROI_TRIG_FP32): the environment is
+ * read once per process, by whichever comes first -- this call or the first launcher call -- so the answer is what every
+ * launcher call of the process uses.  For a caller that computes a launcher call's gradient through the native entry
+ * points (the Python glue under torch.use_deterministic_algorithms). */
+int rroi_align_launcher_trig_recipe(void);
+/* RROI_PATH_DETERMINISTIC (backward): the ORDERED plan, a gradient that does not change from run to run.
+ * Every feature-gradient element (b, c, y, x) is the sum of the fp32 products w * g that reach it, added in DOUBLE from
+ * +0.0 in statement order -- ROI n, pooled row ph, pooled column pw, tap lt / rt / rb / lb -- and rounded to fp32 once:
+ * what the oracle's rroi_oracle_backward computes, bit for bit (NaN where it has NaN), whatever the layouts, the grid,
+ * the CU count, the stream or a graph capture.  Masks and aliases are the reference's (kernel.cu:267-274, and the extra
+ * 0 * g of two taps on one pixel).  A 16-bit call rounds that fp32 gradient of the widened top_diff once to its type.
+ * Accepted with RROI_PATH_AUTO (| RROI_PATH_TRIG_FP32) from the native backward entry points and their plan queries,
+ * every dtype and layout pair, wherever the call without the bit is accepted and the gather's 32-bit indices hold (the
+ * rule 16-bit calls follow): plan RROI_PLAN_BWD_ORDERED for R >= 1, the zero fill for R = 0.  Refused (0) with an
+ * explicit path and by RROI_CALLER_LAUNCHER; a 0.10.0 library refuses the bit itself, which is how a caller detects it.
+ * The workspace is rroi_align_backward_workspace_bytes' (the exact lists' storage).  RROIAlignBackwardLaucher has no
+ * `path`: it stays the reference's non-deterministic scatter order.
+ * The forward needs no such flag: it writes every crop element once, with no atomics in its arithmetic (its ROI sort
+ * only picks the workgroup that serves a ROI), so every forward plan is deterministic already.  The forward entry
+ * points and rroi_align_forward_plan* keep refusing the bit as an unknown flag, as 0.10.0 did. */
+#define RROI_PATH_DETERMINISTIC 0x200
 
 /* Bytes of scratch the tiled path needs for this problem (0 for the direct
  * path).  The caller owns the scratch; its contents are dead after the call. */
@@ -218,6 +239,7 @@ int rroi_align_backward_layout_hip(const float* top_diff, int top_diff_layout, i
 #define RROI_PLAN_BWD_LISTS 14        /* count / scan (+ rroi_scan2_kernel where !plan.raw_bsum) / fill + gather */
 #define RROI_PLAN_BWD_BUCKETS 15      /* one-pass buckets of 1 << plan.kshift + overflow chains + gather  */
 #define RROI_PLAN_BWD_LITERAL 16      /* the backward launcher's per-element kernel (reads con_idx)       */
+#define RROI_PLAN_BWD_ORDERED 17      /* RROI_PATH_DETERMINISTIC: count / scan / fill, the lists sorted by bin, in-order fp64 gather */
 /* plan.kernel: the gather instantiation of the fused / two-launch forward (-1: none) */
 #define RROI_PLAN_KERNEL_STRIDED 0
 #define RROI_PLAN_KERNEL_CHANNELS_LAST 1
