@@ -1689,12 +1689,11 @@ int rroi_align_gt_quads_to_rois_hip(const float* quads, const float* batch_index
     return launch_status();
 }
 
-int rroi_rbox_decode_hip(const float* segm, const float* rbox, const float* angle, int height, int width,
-                         float segm_thresh, void* candidates, int capacity, int* count, void* stream_)
+// one decode call for maps of element type T (float: the kernels of every release; bf16_t / fp16_t: the typed ones)
+extern "C++" template <class T>
+static int rbox_decode_impl(const T* segm, const T* rbox, const T* angle, int height, int width, float segm_thresh,
+                            void* candidates, int capacity, int* count, hipStream_t stream)
 {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (height <= 0 || width <= 0 || capacity < 0 || (long)height * width >= (1L << 30)) return 0;
-    if (!segm || !rbox || !angle || !count || (capacity > 0 && !candidates)) return 0;
     const int hw = height * width;
     const int slabs = ceil_div(hw, 1024);
     unsigned* slab_counts = nullptr;
@@ -1704,13 +1703,44 @@ int rroi_rbox_decode_hip(const float* segm, const float* rbox, const float* angl
     // keeps the one-launch form, in which every workgroup counts the pixels before its slab itself.
     if (slabs > 256 && (long)capacity >= (long)hw + ceil_div((long)slabs * 4, 64)) {
         slab_counts = reinterpret_cast<unsigned*>(static_cast<NmsCandidate*>(candidates) + hw);
-        hipLaunchKernelGGL(rroi_rbox_count_kernel, dim3(slabs), dim3(1024), 0, stream, segm, hw, segm_thresh, slab_counts);
+        if constexpr (sizeof(T) == 4)
+            hipLaunchKernelGGL(rroi_rbox_count_kernel, dim3(slabs), dim3(1024), 0, stream, segm, hw, segm_thresh, slab_counts);
+        else
+            hipLaunchKernelGGL(rroi_rbox_count_typed_kernel<T>, dim3(slabs), dim3(1024), 0, stream, segm, hw, segm_thresh,
+                               slab_counts);
         const int st = launch_status();
         if (st != 1) return st;
     }
-    hipLaunchKernelGGL(rroi_rbox_decode_kernel, dim3(slabs), dim3(1024), 0, stream, segm, rbox, angle, height, width,
-                       segm_thresh, static_cast<NmsCandidate*>(candidates), slab_counts ? hw : capacity, count, slab_counts);
+    if constexpr (sizeof(T) == 4)
+        hipLaunchKernelGGL(rroi_rbox_decode_kernel, dim3(slabs), dim3(1024), 0, stream, segm, rbox, angle, height, width,
+                           segm_thresh, static_cast<NmsCandidate*>(candidates), slab_counts ? hw : capacity, count, slab_counts);
+    else
+        hipLaunchKernelGGL(rroi_rbox_decode_typed_kernel<T>, dim3(slabs), dim3(1024), 0, stream, segm, rbox, angle, height,
+                           width, segm_thresh, static_cast<NmsCandidate*>(candidates), slab_counts ? hw : capacity, count,
+                           slab_counts);
     return launch_status();
+}
+
+int rroi_rbox_decode_typed_hip(int dtype, const void* segm, const void* rbox, const void* angle, int height, int width,
+                               float segm_thresh, void* candidates, int capacity, int* count, void* stream_)
+{
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!dtype_ok(dtype)) return 0;
+    if (height <= 0 || width <= 0 || capacity < 0 || (long)height * width >= (1L << 30)) return 0;
+    if (!segm || !rbox || !angle || !count || (capacity > 0 && !candidates)) return 0;
+    auto run = [&](auto tag) {
+        typedef decltype(tag) T;
+        return rbox_decode_impl<T>(static_cast<const T*>(segm), static_cast<const T*>(rbox), static_cast<const T*>(angle),
+                                   height, width, segm_thresh, candidates, capacity, count, stream);
+    };
+    return dtype == RROI_DTYPE_BF16 ? run(bf16_t{}) : dtype == RROI_DTYPE_FP16 ? run(fp16_t{}) : run(float{});
+}
+
+int rroi_rbox_decode_hip(const float* segm, const float* rbox, const float* angle, int height, int width,
+                         float segm_thresh, void* candidates, int capacity, int* count, void* stream_)
+{
+    return rroi_rbox_decode_typed_hip(RROI_DTYPE_FP32, segm, rbox, angle, height, width, segm_thresh, candidates, capacity,
+                                      count, stream_);
 }
 
 int rroi_nms_record_format(void) { return RROI_NMS_RECORD_FORMAT; }
@@ -1736,18 +1766,33 @@ int rroi_nms_merge_host(const void* candidates, int num_candidates, int width, i
     return n;
 }
 
-int rroi_ctc_greedy_decode_hip(const float* logits, int num_seqs, int num_classes, int num_steps,
-                               const int* lengths, int* labels, int* decoded, int* decoded_len,
-                               void* stream_)
+int rroi_ctc_greedy_decode_typed_hip(int dtype, const void* logits, int num_seqs, int num_classes, int num_steps,
+                                     const int* lengths, int* labels, int* decoded, int* decoded_len, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!dtype_ok(dtype)) return 0;
     if (num_seqs < 0 || num_classes <= 0 || num_steps < 0) return 0;
     if ((long)num_seqs * num_classes * (long)num_steps >= (1L << 40)) return 0;
     if (num_seqs == 0) return 1;
     if (!decoded_len || (num_steps > 0 && (!logits || !decoded))) return 0;
-    hipLaunchKernelGGL(rroi_ctc_greedy_kernel, dim3(num_seqs), dim3(kWave), 0, stream, logits,
-                       num_classes, num_steps, lengths, labels, decoded, decoded_len);
+    if (dtype == RROI_DTYPE_BF16)
+        hipLaunchKernelGGL(rroi_ctc_greedy_typed_kernel<bf16_t>, dim3(num_seqs), dim3(kWave), 0, stream,
+                           static_cast<const bf16_t*>(logits), num_classes, num_steps, lengths, labels, decoded, decoded_len);
+    else if (dtype == RROI_DTYPE_FP16)
+        hipLaunchKernelGGL(rroi_ctc_greedy_typed_kernel<fp16_t>, dim3(num_seqs), dim3(kWave), 0, stream,
+                           static_cast<const fp16_t*>(logits), num_classes, num_steps, lengths, labels, decoded, decoded_len);
+    else
+        hipLaunchKernelGGL(rroi_ctc_greedy_kernel, dim3(num_seqs), dim3(kWave), 0, stream, static_cast<const float*>(logits),
+                           num_classes, num_steps, lengths, labels, decoded, decoded_len);
     return launch_status();
+}
+
+int rroi_ctc_greedy_decode_hip(const float* logits, int num_seqs, int num_classes, int num_steps,
+                               const int* lengths, int* labels, int* decoded, int* decoded_len,
+                               void* stream_)
+{
+    return rroi_ctc_greedy_decode_typed_hip(RROI_DTYPE_FP32, logits, num_seqs, num_classes, num_steps, lengths, labels,
+                                            decoded, decoded_len, stream_);
 }
 
 int rroi_align_write_probe_hip(float* out, size_t num_floats, void* stream_)

@@ -124,14 +124,19 @@ __global__ void rroi_bin_centres_kernel(const float* __restrict__ rois, float* _
 // are contiguous in t); arg max = first index of the largest value, NaN counting as largest
 // (torch.max); the kept labels are compacted with a ballot + popcount prefix.
 // ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kWave) void rroi_ctc_greedy_kernel(
-    const float* __restrict__ logits, int nclass, int T, const int* __restrict__ lengths,
+// E: the logits' element type (after 0.10.0: bf16_t / fp16_t, the output of a head that runs in 16 bits).  Lanes stay
+// time steps and a lane takes ONE element per class -- a wave's 64 lanes read 128 contiguous bytes of a class row --, so
+// a row that starts on a 2-byte boundary (odd T) needs nothing special; the element is widened exactly and compared in
+// fp32 as below (widening is monotonic, keeps ties ties and a NaN a NaN).
+template <class E>
+__device__ __forceinline__ void ctc_greedy_body(
+    const E* __restrict__ logits, int nclass, int T, const int* __restrict__ lengths,
     int* __restrict__ labels, int* __restrict__ decoded, int* __restrict__ decoded_len)
 {
     const unsigned n = blockIdx.x, lane = threadIdx.x;
     int len = lengths ? lengths[n] : T;
     len = len < 0 ? 0 : (len > T ? T : len);
-    const float* row = logits + (size_t)n * nclass * T;
+    const E* row = logits + (size_t)n * nclass * T;
     int* lab = labels ? labels + (size_t)n * T : nullptr;
     int* dec = decoded + (size_t)n * T;
     unsigned out = 0;
@@ -140,10 +145,10 @@ __global__ __launch_bounds__(kWave) void rroi_ctc_greedy_kernel(
         const int t = t0 + (int)lane;
         int best = 0;
         if (t < T) {
-            float bv = row[t];
+            float bv = to_f32(row[t]);
             bool bnan = bv != bv;
             for (int k = 1; k < nclass; ++k) {
-                const float v = row[(size_t)k * T + t];
+                const float v = to_f32(row[(size_t)k * T + t]);
                 const bool vnan = v != v;
                 if (!bnan && (vnan || v > bv)) {
                     bv = v;
@@ -163,6 +168,21 @@ __global__ __launch_bounds__(kWave) void rroi_ctc_greedy_kernel(
     }
     for (unsigned i = out + lane; i < (unsigned)T; i += kWave) dec[i] = 0;  // padding
     if (lane == 0) decoded_len[n] = (int)out;
+}
+
+__global__ __launch_bounds__(kWave) void rroi_ctc_greedy_kernel(
+    const float* __restrict__ logits, int nclass, int T, const int* __restrict__ lengths,
+    int* __restrict__ labels, int* __restrict__ decoded, int* __restrict__ decoded_len)
+{
+    ctc_greedy_body<float>(logits, nclass, T, lengths, labels, decoded, decoded_len);
+}
+
+template <class E>
+__global__ __launch_bounds__(kWave) void rroi_ctc_greedy_typed_kernel(
+    const E* __restrict__ logits, int nclass, int T, const int* __restrict__ lengths,
+    int* __restrict__ labels, int* __restrict__ decoded, int* __restrict__ decoded_len)
+{
+    ctc_greedy_body<E>(logits, nclass, T, lengths, labels, decoded, decoded_len);
 }
 
 __global__ void rroi_sincos_probe_kernel(const float* __restrict__ deg, int n, float* __restrict__ out)

@@ -279,6 +279,8 @@ typedef __bf16 bf16_t;
 typedef _Float16 fp16_t;
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
 template <class T> struct Vec4 { typedef T type __attribute__((ext_vector_type(4))); };
+template <class T> struct Vec8 { typedef T type __attribute__((ext_vector_type(8))); };   // 16 bytes of a 16-bit type
+typedef float v8f __attribute__((ext_vector_type(8)));
 
 template <class T>
 __device__ __forceinline__ float to_f32(T x) { return (float)x; }

@@ -33,8 +33,13 @@ struct NmsCandidate {  // 64 bytes
 };
 static_assert(sizeof(NmsCandidate) == 64, "one candidate = one 64-byte record");
 
-// number of pixels of segm[lo, hi) above the threshold, counted by the whole workgroup (1024 threads)
-__device__ __forceinline__ unsigned nms_count_passing(const float* __restrict__ segm, int lo, int hi, float thr,
+// number of pixels of segm[lo, hi) above the threshold, counted by the whole workgroup (1024 threads).
+// T: the map's element type (after 0.10.0: bf16_t / fp16_t maps of a 16-bit detector, widened exactly where they are
+// loaded and compared in fp32).  The 16-byte load stays: four fp32 pixels, or EIGHT 16-bit pixels (8192 per step).  A
+// map whose base is not 16-byte aligned -- image i of a batch whose h * w is odd starts on a 2-byte boundary -- takes
+// the scalar loop for all of it; lo is a multiple of 1024, so an aligned base keeps every vector load aligned.
+template <class T>
+__device__ __forceinline__ unsigned nms_count_passing(const T* __restrict__ segm, int lo, int hi, float thr,
                                                       unsigned* wave_total)
 {
     const unsigned tid = threadIdx.x;
@@ -42,12 +47,21 @@ __device__ __forceinline__ unsigned nms_count_passing(const float* __restrict__ 
     const bool vec = (reinterpret_cast<uintptr_t>(segm) & 15) == 0;
     int p = lo;
     if (vec) {
-        for (; p + 4096 <= hi; p += 4096) {
-            const v4f v = *reinterpret_cast<const v4f*>(segm + p + 4 * (int)tid);
-            n += (v.x > thr) + (v.y > thr) + (v.z > thr) + (v.w > thr);
+        if constexpr (sizeof(T) == 4) {
+            for (; p + 4096 <= hi; p += 4096) {
+                const v4f v = *reinterpret_cast<const v4f*>(segm + p + 4 * (int)tid);
+                n += (v.x > thr) + (v.y > thr) + (v.z > thr) + (v.w > thr);
+            }
+        } else {
+            typedef typename Vec8<T>::type vt;
+            for (; p + 8192 <= hi; p += 8192) {
+                const v8f v = __builtin_convertvector(*reinterpret_cast<const vt*>(segm + p + 8 * (int)tid), v8f);
+                n += (v[0] > thr) + (v[1] > thr) + (v[2] > thr) + (v[3] > thr);
+                n += (v[4] > thr) + (v[5] > thr) + (v[6] > thr) + (v[7] > thr);
+            }
         }
     }
-    for (; p < hi; p += 1024) n += (p + (int)tid < hi && segm[p + (int)tid] > thr) ? 1u : 0u;
+    for (; p < hi; p += 1024) n += (p + (int)tid < hi && to_f32(segm[p + (int)tid]) > thr) ? 1u : 0u;
 #pragma unroll
     for (int o = 32; o; o >>= 1) n += __shfl_xor(n, o);
     if ((tid & 63u) == 0) wave_total[tid >> 6] = n;
@@ -59,12 +73,14 @@ __device__ __forceinline__ unsigned nms_count_passing(const float* __restrict__ 
 }
 
 // slab_counts == nullptr: count the pixels before this slab here; else slab_counts[j] = passing pixels of slab j
-__global__ __launch_bounds__(1024) void rroi_rbox_decode_kernel(
-    const float* __restrict__ segm, const float* __restrict__ rbox, const float* __restrict__ angle, int h, int w,
+// (the body of the decode kernels: T = float is rroi_rbox_decode_kernel, bf16_t / fp16_t the typed one below; a 16-bit
+// element is widened where it is loaded and every statement after the load is the fp32 kernel's)
+template <class T>
+__device__ __forceinline__ void rbox_decode_body(
+    const T* __restrict__ segm, const T* __restrict__ rbox, const T* __restrict__ angle, int h, int w,
     float segm_thresh, NmsCandidate* __restrict__ out, int capacity, int* __restrict__ count,
-    const unsigned* __restrict__ slab_counts)
+    const unsigned* __restrict__ slab_counts, unsigned* wave_total)
 {
-    __shared__ unsigned wave_total[16];
     const unsigned tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
     const int hw = h * w;
     const int p0 = (int)blockIdx.x * 1024;
@@ -84,7 +100,7 @@ __global__ __launch_bounds__(1024) void rroi_rbox_decode_kernel(
     }
     {
         const int p = p0 + (int)tid;
-        const bool pass = p < hw && segm[p] > segm_thresh;
+        const bool pass = p < hw && to_f32(segm[p]) > segm_thresh;
         const unsigned long long m = __ballot(pass);
         if (lane == 0) wave_total[wv] = (unsigned)__popcll(m);
         __syncthreads();
@@ -98,8 +114,8 @@ __global__ __launch_bounds__(1024) void rroi_rbox_decode_kernel(
         if (pass && slot < (unsigned)capacity) {
             const int y = p / w, x = p - y * w;
             const size_t q = (size_t)p, n = (size_t)hw;
-            const float r0 = rbox[q], r1 = rbox[n + q], r2 = rbox[2 * n + q], r3 = rbox[3 * n + q];
-            const float angle_sin = angle[q], angle_cos = angle[n + q];   // a[0], a[1] (:84-85)
+            const float r0 = to_f32(rbox[q]), r1 = to_f32(rbox[n + q]), r2 = to_f32(rbox[2 * n + q]), r3 = to_f32(rbox[3 * n + q]);
+            const float angle_sin = to_f32(angle[q]), angle_cos = to_f32(angle[n + q]);   // a[0], a[1] (:84-85)
             const float scale_factor = 4.0f, precision = 10000.0f;
             const float xp = (float)x + 0.25f, yp = (float)y + 0.25f;
             const float pos_r_x = (xp - r2 * angle_cos) * scale_factor;
@@ -115,7 +131,7 @@ __global__ __launch_bounds__(1024) void rroi_rbox_decode_kernel(
             c.quad[5] = (int)roundf(precision * (pos_r2_y - r0 * angle_cos * scale_factor));
             c.quad[6] = (int)roundf(precision * (pos_r2_x - r1 * angle_sin * scale_factor));
             c.quad[7] = (int)roundf(precision * (pos_r2_y + r1 * angle_cos * scale_factor));
-            c.score = segm[p];
+            c.score = to_f32(segm[p]);
             c.rdist[0] = r0;
             c.rdist[1] = r1;
             c.rdist[2] = r2;
@@ -130,9 +146,39 @@ __global__ __launch_bounds__(1024) void rroi_rbox_decode_kernel(
     }
 }
 
+__global__ __launch_bounds__(1024) void rroi_rbox_decode_kernel(
+    const float* __restrict__ segm, const float* __restrict__ rbox, const float* __restrict__ angle, int h, int w,
+    float segm_thresh, NmsCandidate* __restrict__ out, int capacity, int* __restrict__ count,
+    const unsigned* __restrict__ slab_counts)
+{
+    __shared__ unsigned wave_total[16];
+    rbox_decode_body<float>(segm, rbox, angle, h, w, segm_thresh, out, capacity, count, slab_counts, wave_total);
+}
+
+// the maps of a 16-bit detector (T = bf16_t / fp16_t; all three maps of a call have one type)
+template <class T>
+__global__ __launch_bounds__(1024) void rroi_rbox_decode_typed_kernel(
+    const T* __restrict__ segm, const T* __restrict__ rbox, const T* __restrict__ angle, int h, int w,
+    float segm_thresh, NmsCandidate* __restrict__ out, int capacity, int* __restrict__ count,
+    const unsigned* __restrict__ slab_counts)
+{
+    __shared__ unsigned wave_total[16];
+    rbox_decode_body<T>(segm, rbox, angle, h, w, segm_thresh, out, capacity, count, slab_counts, wave_total);
+}
+
 // maps beyond 256 K pixels: passing pixels per 1024-pixel slab (the decode launch then sums the slabs before its own)
 __global__ __launch_bounds__(1024) void rroi_rbox_count_kernel(const float* __restrict__ segm, int hw, float segm_thresh,
                                                               unsigned* __restrict__ slab_counts)
+{
+    __shared__ unsigned wave_total[16];
+    const int p0 = (int)blockIdx.x * 1024;
+    const unsigned total = nms_count_passing(segm, p0, min(hw, p0 + 1024), segm_thresh, wave_total);
+    if (threadIdx.x == 0) slab_counts[blockIdx.x] = total;
+}
+
+template <class T>
+__global__ __launch_bounds__(1024) void rroi_rbox_count_typed_kernel(const T* __restrict__ segm, int hw, float segm_thresh,
+                                                                    unsigned* __restrict__ slab_counts)
 {
     __shared__ unsigned wave_total[16];
     const int p0 = (int)blockIdx.x * 1024;

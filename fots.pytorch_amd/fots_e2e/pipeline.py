@@ -41,9 +41,10 @@ def resize_rule(h0, w0, max_size=1585152, scale_up=False):
     return int(size[1]), int(size[0])
 
 
-def preprocess(im_u8, device):
-    """(H0, W0, 3) uint8 -> (1, 3, H, W) fp32 = resized / 128 - 1 (test.py:77-83).  The resize is
-    half-pixel bilinear like cv2.resize's default, done on the device."""
+def preprocess(im_u8, device, dtype=torch.float32):
+    """(H0, W0, 3) uint8 -> (1, 3, H, W) = resized / 128 - 1 (test.py:77-83).  The resize is
+    half-pixel bilinear like cv2.resize's default, done on the device.  `dtype`: of the network that takes the image
+    (float32, bfloat16, float16): resize and scaling run in fp32 whatever it is, and the result is rounded ONCE."""
     # the BYTES go up (a quarter of the fp32 image) and are widened on the device: `.to(device, dtype)` in one step converts
     # on the host first -- a parallel region of torch's intra-op pool per image, whose spinning workers are what a
     # CPU-quota'd container gets throttled for (hostcpus.py; round 6: batches of images took 36 or 70 ms at random)
@@ -51,7 +52,14 @@ def preprocess(im_u8, device):
     h, w = resize_rule(t.shape[2], t.shape[3])
     if (h, w) != tuple(t.shape[2:]):
         t = F.interpolate(t, size=(h, w), mode="bilinear", align_corners=False)
-    return t / 128 - 1
+    t = t / 128 - 1
+    return t if dtype == torch.float32 else t.to(dtype)
+
+
+def _net_device_dtype(net):
+    """Where the network lives and the dtype it runs in (`net.to(torch.bfloat16)`): its first parameter's."""
+    p = next(net.parameters())
+    return p.device, p.dtype
 
 
 def target_widths_host(boxes):
@@ -73,6 +81,9 @@ def batched(net, converter, features, boxes, return_crops=False, gw_host=None, b
     `gw_host`: the boxes' pooled widths when the caller already has them on the host (`infer_image`:
     the boxes come out of the host-side merge: `target_widths_host`) -- then nothing is
     read back before the head.
+    A network in bfloat16 / float16 hands 16-bit features over: the op cuts 16-bit crops natively (each element the fp32
+    crop's, rounded once), the head runs in 16 bits and the greedy CTC reads its 16-bit log-probabilities as they are --
+    no widening copy anywhere on the path.  Quads, ROI rows and widths are float32 / int32: they carry geometry.
     `batch_index` (N,): the image each box belongs to when `features` hold SEVERAL images (`infer_batch`) -- the op's
     own first ROI column (`tools/ocr_utils.py:151` writes 0 there: one image per call); still ONE RoIRotate launch."""
     focr = features[1]
@@ -127,10 +138,14 @@ def infer_image(net, converter, im, detector=None, segm_thresh=0.5, return_debug
     Host synchronisations per image: ONE before the head (`get_boxes` reads the number of passing pixels
     and their records: the merge is sequential host code) and the final read-back of the decoded labels.
     The pooled-width buckets need no second one: the boxes are on the host after the merge and the width
-    rule is plain arithmetic (`target_widths_host`)."""
+    rule is plain arithmetic (`target_widths_host`).
+
+    The image is preprocessed into the dtype of the network's parameters (float32, bfloat16, float16), so
+    `infer_image(net.to(torch.bfloat16), ...)` runs the whole chain in 16 bits with the same synchronisations; a tensor
+    passed instead of an image is used as it is.  The `detector` hook's maps may have any of the three dtypes."""
     from rroi_align.nms import get_boxes
-    device = next(net.parameters()).device
-    im_data = preprocess(im, device) if not isinstance(im, torch.Tensor) else im
+    device, dtype = _net_device_dtype(net)
+    im_data = preprocess(im, device, dtype) if not isinstance(im, torch.Tensor) else im
     score, rbox, angle, feats = net(im_data)
     if detector is not None:
         s, r, a = detector(im_data)
@@ -148,14 +163,14 @@ def _batch_front(net, ims, detector, segm_thresh):
     """The first half of `infer_batch`, ENQUEUED on the current stream and nothing read back: preprocessing, one pass of the
     network, one decode launch per image."""
     from rroi_align.nms import decode_batch
-    device = next(net.parameters()).device
+    device, dtype = _net_device_dtype(net)
     if isinstance(ims, torch.Tensor):
         im_data = ims
     else:
         sizes = {resize_rule(im.shape[0], im.shape[1]) for im in ims}
         if len(sizes) != 1:
             raise ValueError("infer_batch: the images must resize to one size, got %s (group them by size)" % sorted(sizes))
-        im_data = torch.cat([preprocess(im, device) for im in ims], 0)
+        im_data = torch.cat([preprocess(im, device, dtype) for im in ims], 0)
     score, rbox, angle, feats = net(im_data)
     if detector is not None:
         s, r, a = detector(im_data)
@@ -213,6 +228,16 @@ def infer_stream(net, converter, batches, detector=None, segm_thresh=0.5):
     side = torch.cuda.Stream(device=device)
 
     def back(front, ready):
+        # INVARIANT: everything `side` reads was allocated on the caller's stream -- the feature maps and each image's
+        # (records, count).  `ready` orders the reads after their producers; record_stream tells the caching allocator
+        # that `side` uses the blocks too, so that a tensor the caller's stream frees (the generator drops `front`
+        # while batch k + 1's network pass is being enqueued) is not handed out again before `side` is done with it.
+        _, feats, (pending, _) = front
+        for t in feats:
+            t.record_stream(side)
+        for rec, cnt in pending:
+            rec.record_stream(side)
+            cnt.record_stream(side)
         with torch.cuda.stream(side):
             side.wait_event(ready)
             res = _batch_back(net, converter, front)      # its read-backs synchronise `side` only

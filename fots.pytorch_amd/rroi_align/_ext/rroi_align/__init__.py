@@ -119,6 +119,11 @@ _lib.rroi_align_forward_typed_hip.restype = _i
 _lib.rroi_align_forward_typed_hip.argtypes = [_vp, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _vp]
 _lib.rroi_align_backward_typed_hip.restype = _i
 _lib.rroi_align_backward_typed_hip.argtypes = [_vp, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _vp]
+# the callers' kernels on bfloat16 / float16 data (after 0.10.0, same version string: found by symbol)
+_lib.rroi_rbox_decode_typed_hip.restype = _i
+_lib.rroi_rbox_decode_typed_hip.argtypes = [_i, _vp, _vp, _vp, _i, _i, _f, _vp, _i, _vp, _vp]
+_lib.rroi_ctc_greedy_decode_typed_hip.restype = _i
+_lib.rroi_ctc_greedy_decode_typed_hip.argtypes = [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]
 
 EXPORTS = (
     "RROIAlignForwardLaucher", "RROIAlignBackwardLaucher", "rroi_align_forward_hip",
@@ -134,6 +139,7 @@ EXPORTS = (
     "rroi_align_forward_typed_hip", "rroi_align_backward_typed_hip",
     "rroi_align_forward_plan_typed", "rroi_align_backward_plan_typed",
     "rroi_align_launcher_trig_recipe",
+    "rroi_rbox_decode_typed_hip", "rroi_ctc_greedy_decode_typed_hip",
 )
 
 # What a call launches (rroi_align_forward_plan / rroi_align_backward_plan); the fields of rroi_align_plan.
@@ -402,10 +408,13 @@ def bin_centres(rois: torch.Tensor, pooled_height: int, pooled_width: int, spati
 
 
 def ctc_greedy_decode(logits: torch.Tensor, lengths=None, return_labels: bool = False):
-    """(N, nclass, T) fp32 logits -> (decoded (N, T) int32 zero-padded, decoded_len (N,) int32
+    """(N, nclass, T) logits -> (decoded (N, T) int32 zero-padded, decoded_len (N,) int32
     [, raw arg-max labels (N, T) int32]), all on the device; one launch for all sequences.
-    Replaces `labels_pred.max(1)` + strLabelConverter.decode (tools/ocr_utils.py:183-186)."""
-    _require_cuda_f32(logits, "logits")
+    Replaces `labels_pred.max(1)` + strLabelConverter.decode (tools/ocr_utils.py:183-186).
+    logits: float32, bfloat16 or float16 (a head that runs in 16 bits): a 16-bit element is widened exactly where the
+    kernel loads it, so the result is that of the float32 call on `logits.float()`, ties and NaN included."""
+    _require_cuda_f32(logits, "logits", _IO_DTYPES)
+    code = _DTYPES[logits.dtype]
     if logits.dim() != 3:
         raise ValueError("logits must be (N, nclass, T)")
     logits = logits.contiguous()
@@ -421,11 +430,13 @@ def ctc_greedy_decode(logits: torch.Tensor, lengths=None, return_labels: bool = 
         decoded = torch.empty((N, T), dtype=torch.int32, device=dev)
         dlen = torch.empty((N,), dtype=torch.int32, device=dev)
         labels = torch.empty((N, T), dtype=torch.int32, device=dev) if return_labels else None
-        st = _lib.rroi_ctc_greedy_decode_hip(
-            logits.data_ptr(), N, K, T, lengths.data_ptr() if lengths is not None else None,
-            labels.data_ptr() if labels is not None else None, decoded.data_ptr(), dlen.data_ptr(),
-            _stream())
-    _check(st, "rroi_ctc_greedy_decode_hip")
+        tail = (N, K, T, lengths.data_ptr() if lengths is not None else None,
+                labels.data_ptr() if labels is not None else None, decoded.data_ptr(), dlen.data_ptr(), _stream())
+        if code == DTYPE_FP32:
+            st = _lib.rroi_ctc_greedy_decode_hip(logits.data_ptr(), *tail)
+        else:
+            st = _lib.rroi_ctc_greedy_decode_typed_hip(code, logits.data_ptr(), *tail)
+    _check(st, "rroi_ctc_greedy_decode_hip" if code == DTYPE_FP32 else "rroi_ctc_greedy_decode_typed_hip")
     return (decoded, dlen, labels) if return_labels else (decoded, dlen)
 
 

@@ -16,7 +16,8 @@ from ._ext import rroi_align as _ext
 
 
 def ctc_greedy_decode(logits, lengths=None, return_labels=False):
-    """(N, nclass, T) fp32 -> (decoded (N, T) int32 zero-padded, decoded_len (N,) int32[, labels])."""
+    """(N, nclass, T) float32, bfloat16 or float16 -> (decoded (N, T) int32 zero-padded, decoded_len (N,) int32[, labels]).
+    16-bit logits are widened exactly inside the kernel: the result is that of `logits.float()`."""
     return _ext.ctc_greedy_decode(logits, lengths, return_labels)
 
 
@@ -29,7 +30,7 @@ class CTCLabelConverter(object):
         self.dict = {char: i + 1 for i, char in enumerate(alphabet)}
 
     def decode_logits(self, logits, lengths=None):
-        """logits (N, nclass, T) on the GPU -> list of N strings (one kernel, one copy)."""
+        """logits (N, nclass, T) on the GPU (float32, bfloat16 or float16) -> list of N strings (one kernel, one copy)."""
         decoded, dlen = ctc_greedy_decode(logits, lengths)
         return self.to_texts(decoded, dlen)
 

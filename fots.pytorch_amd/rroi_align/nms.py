@@ -22,10 +22,16 @@ assert CANDIDATE.itemsize == 64
 
 
 def decode(score, rbox, angle, segm_thresh=0.5):
-    """score (h, w), rbox (4, h, w), angle (2, h, w) fp32 on the GPU -> (records uint8 (h*w, 64) on
-    the GPU, count int32 (1,) on the GPU): the candidates of adaptor.cpp:76-117 in raster order."""
+    """score (h, w), rbox (4, h, w), angle (2, h, w) on the GPU -> (records uint8 (h*w, 64) on
+    the GPU, count int32 (1,) on the GPU): the candidates of adaptor.cpp:76-117 in raster order.
+    The maps are float32, or -- a detector that runs in 16 bits -- bfloat16 / float16, all three of ONE dtype: a 16-bit
+    element is widened exactly where the kernel loads it, so count and records are byte for byte those of the widened
+    maps (`score.float()`, ...); the records' score and distances stay fp32."""
     for t, name in ((score, "score"), (rbox, "rbox"), (angle, "angle")):
-        _ext._require_cuda_f32(t, name)
+        _ext._require_cuda_f32(t, name, _ext._IO_DTYPES)
+    if not (score.dtype == rbox.dtype == angle.dtype):
+        raise TypeError("score, rbox and angle must have one dtype, got %s, %s and %s" % (score.dtype, rbox.dtype, angle.dtype))
+    code = _ext._DTYPES[score.dtype]
     h, w = score.shape[-2:]
     score, rbox, angle = score.reshape(h, w).contiguous(), rbox.reshape(4, h, w).contiguous(), angle.reshape(2, h, w).contiguous()
     slabs = (h * w + 1023) // 1024
@@ -34,9 +40,13 @@ def decode(score, rbox, angle, segm_thresh=0.5):
     with torch.cuda.device_of(score):
         rec = torch.empty((cap, 64), dtype=torch.uint8, device=score.device)
         cnt = torch.empty((1,), dtype=torch.int32, device=score.device)
-        st = _ext._lib.rroi_rbox_decode_hip(score.data_ptr(), rbox.data_ptr(), angle.data_ptr(), h, w,
-                                            float(segm_thresh), rec.data_ptr(), cap, cnt.data_ptr(), _ext._stream())
-    _ext._check(st, "rroi_rbox_decode_hip")
+        tail = (score.data_ptr(), rbox.data_ptr(), angle.data_ptr(), h, w, float(segm_thresh), rec.data_ptr(), cap,
+                cnt.data_ptr(), _ext._stream())
+        if code == _ext.DTYPE_FP32:
+            st = _ext._lib.rroi_rbox_decode_hip(*tail)
+        else:
+            st = _ext._lib.rroi_rbox_decode_typed_hip(code, *tail)
+    _ext._check(st, "rroi_rbox_decode_hip" if code == _ext.DTYPE_FP32 else "rroi_rbox_decode_typed_hip")
     return rec, cnt
 
 
@@ -57,7 +67,7 @@ def merge(records, width, height, iou_threshold=0.4, iou_threshold2=0.2):
 
 def get_boxes(iou_map, rbox, angle_pred, segm_thresh=0.5):
     """`nms.get_boxes` (nms/__init__.py:20-29).  Device tensors in the network's own layout --
-    iou_map (h, w), rbox (4, h, w), angle_pred (2, h, w) -- or, for call-site compatibility, the
+    iou_map (h, w), rbox (4, h, w), angle_pred (2, h, w), float32 or (all three) bfloat16 / float16 -- or, for call-site compatibility, the
     reference's numpy arrays (rbox as (h, w, 4)), which are uploaded first.  -> (n, 9) numpy fp32."""
     if not isinstance(iou_map, torch.Tensor):
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -113,7 +123,7 @@ def merge_decoded(decoded):
 
 def get_boxes_batch(iou_map, rbox, angle_pred, segm_thresh=0.5):
     """`get_boxes` for the maps of SEVERAL images -- iou_map (N, h, w), rbox (N, 4, h, w), angle_pred (N, 2, h, w) on the
-    GPU -- with TWO host synchronisations for the batch instead of two per image: every image's decode launch is
+    GPU, float32 or (all three) bfloat16 / float16 -- with TWO host synchronisations for the batch instead of two per image: every image's decode launch is
     enqueued first (`decode_batch`), then `merge_decoded`.
     -> a list of N (n_i, 9) numpy fp32 arrays, each equal to `get_boxes` of that image's maps."""
     return merge_decoded(decode_batch(iou_map, rbox, angle_pred, segm_thresh))

@@ -368,6 +368,15 @@ int rroi_rbox_decode_hip(const float* segm, const float* rbox, const float* angl
                          float segm_thresh, void* candidates, int capacity, int* count, void* stream);
 int rroi_nms_merge_host(const void* candidates, int num_candidates, int width, int height, float iou_threshold,
                         float iou_threshold2, float* boxes, int max_boxes);
+/* The maps of a 16-bit detector: `dtype` (RROI_DTYPE_*, section 2) is the element type of ALL THREE maps.  A bfloat16 /
+ * float16 element is widened exactly to fp32 where it is loaded and everything after the load is the fp32 kernel's
+ * arithmetic: count and records are byte for byte those of rroi_rbox_decode_hip on the widened maps (the record stays
+ * RROI_NMS_RECORD_FORMAT 2: score and rdist[4] are the widened fp32 values; `score > segm_thresh` is decided on the
+ * widened value), in both launch forms and for any capacity.  A 16-bit map needs 2-byte alignment only (image i of a
+ * batch whose h * w is odd).  RROI_DTYPE_FP32 IS rroi_rbox_decode_hip; an unknown dtype returns 0 before any launch.
+ * Arrived after 0.10.0 without a new version string: detect it by symbol (dlsym). */
+int rroi_rbox_decode_typed_hip(int dtype, const void* segm, const void* rbox, const void* angle, int height, int width,
+                               float segm_thresh, void* candidates, int capacity, int* count, void* stream);
 
 /* Greedy CTC decode of the recognition logits computed from the crops: replaces the per-box
  * `labels_pred.max(1)` + Python loop of tools/ocr_utils.py:183-186 / src/utils.py:87-97
@@ -382,6 +391,12 @@ int rroi_nms_merge_host(const void* candidates, int num_candidates, int width, i
 int rroi_ctc_greedy_decode_hip(const float* logits, int num_seqs, int num_classes, int num_steps,
                                const int* lengths, int* labels, int* decoded, int* decoded_len,
                                void* stream);
+/* ... of bfloat16 / float16 logits (`dtype`: RROI_DTYPE_*), the output of a head that runs in 16 bits: each element is
+ * widened exactly where it is loaded, so labels, decoded and decoded_len are those of rroi_ctc_greedy_decode_hip on the
+ * widened logits, ties and NaN included.  RROI_DTYPE_FP32 IS that call; an unknown dtype returns 0 before any launch.
+ * Arrived after 0.10.0 without a new version string: detect it by symbol (dlsym). */
+int rroi_ctc_greedy_decode_typed_hip(int dtype, const void* logits, int num_seqs, int num_classes, int num_steps,
+                                     const int* lengths, int* labels, int* decoded, int* decoded_len, void* stream);
 
 /* Bin centres only: geom (R, PH, PW, 2) = (bin_cx, bin_cy), 0 where the bin is
  * outside the ROI's pooled width (kernel.cu:86-107).  Diagnostic / test hook. */
@@ -410,7 +425,9 @@ int rroi_align_write_probe_hip(float* out, size_t num_floats, void* stream);
 int rroi_align_set_trig_recipe_hip(int recipe);
 int rroi_align_get_trig_recipe_hip(void);
 
-/* Identification: "rroi_align_hip <version> gfx950" (0.7.0: per-call trig recipe, device-wide setter removed; 0.8.0: launcher scratch reused within a capture, table of 64, stats; 0.9.0: plan query; 0.10.0: bfloat16 / float16 tensors). */
+/* Identification: "rroi_align_hip <version> gfx950" (0.7.0: per-call trig recipe, device-wide setter removed; 0.8.0: launcher scratch reused within a capture, table of 64, stats; 0.9.0: plan query; 0.10.0: bfloat16 / float16 tensors).
+ * The typed callers' entry points (rroi_rbox_decode_typed_hip, rroi_ctc_greedy_decode_typed_hip) arrived after 0.10.0 under
+ * the same version string: a caller detects them by symbol. */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
