@@ -678,11 +678,22 @@ static inline bool gather_choice_is_open(int path)
 // TILED would take, and a problem no gather can index is refused.
 // RROI_PATH_DETERMINISTIC: native AUTO calls only; every R >= 1 runs ORDERED -- the exact lists, sorted,
 // and the in-order fp64 gather, written in place in either layout -- where the gather can index the problem.
+// ragged (the bucketed call): pooled_width is the call's largest width; the gradient crops are NCHW, the
+// caller is native, and the plan is one of the list gathers -- LISTS (named), BUCKETS (named, or where AUTO prefers them),
+// ORDERED (RROI_PATH_DETERMINISTIC) -- whatever the size: the in-kernel gather and the fp32-atomic forms have no ragged
+// form, so AUTO never returns them and every other path is refused.
 BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch_size, int num_rois, int height, int width,
-                          int channels, int pooled_height, int pooled_width, int path, int caller, int dtype = RROI_DTYPE_FP32)
+                          int channels, int pooled_height, int pooled_width, int path, int caller, int dtype = RROI_DTYPE_FP32,
+                          bool ragged = false)
 {
     BwdDispatch P;
     if (!caller_ok(caller, false) || !dtype_ok(dtype)) return P;
+    if (ragged) {
+        const int named = path & 0xff;
+        if (caller != RROI_CALLER_NATIVE || top_diff_layout != RROI_LAYOUT_NCHW ||
+            (named != RROI_PATH_AUTO && named != RROI_PATH_TILED_LISTS && named != RROI_PATH_TILED_BUCKETS))
+            return P;
+    }
     const bool half = dtype != RROI_DTYPE_FP32;
     if (half && (caller != RROI_CALLER_NATIVE || top_diff_layout != RROI_LAYOUT_NCHW ||
                  (path & 0xff) == RROI_PATH_DIRECT || (path & 0xff) == RROI_PATH_TILED_ATOMIC))
@@ -733,7 +744,7 @@ BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch
     const int NB = pooled_height * pooled_width;
     const size_t HW = (size_t)height * width;
     const bool accumulate = P.accumulate;
-    const bool tiled = ordered || half || td_nhwc || bd_nhwc || (path == RROI_PATH_AUTO
+    const bool tiled = ragged || ordered || half || td_nhwc || bd_nhwc || (path == RROI_PATH_AUTO
                                        ? pick_tiled_bwd(batch_size, channels, height, width, num_rois, NB)
                                        : path != RROI_PATH_DIRECT);
     if (accumulate && (!tiled || bd_nhwc)) return P;
@@ -752,6 +763,7 @@ BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch
     if ((td_nhwc || bd_nhwc) && (!ws.gather_ok || (size_t)num_rois * NB >= (1ull << 32))) return P;
     if (half && !ws.gather_ok) return P;   // (the atomic scatter, an fp32 call's fallback, has no 16-bit form)
     if (ordered && !ws.gather_ok) return P;   // (... nor an ordered one)
+    if (ragged && !ws.gather_ok) return P;    // (... nor a ragged one)
     const bool gather = path != RROI_PATH_TILED_ATOMIC && ws.gather_ok;
     // Two gathers.  K3t builds the pixel lists inside the gather kernel (rroi_backward_tile_kernels.h), K3g
     // with count / scan / fill launches in HBM.  Measured (tools/crossover.py, MI355X, us per call,
@@ -784,7 +796,7 @@ BwdDispatch plan_backward(int top_diff_layout, int bottom_diff_layout, int batch
     // that was far enough.
     const bool buckets = !ordered && gather && ws.bucket_ok && gather_choice_is_open(path) &&
                          (path == RROI_PATH_TILED_BUCKETS || (ws.bucket_pref && g_tune.bwd_buckets));
-    const bool lists = ordered || buckets || path == RROI_PATH_TILED_LISTS || !inkernel_ok ||
+    const bool lists = ragged || ordered || buckets || path == RROI_PATH_TILED_LISTS || !inkernel_ok ||
                        (path != RROI_PATH_TILED_INKERNEL && !prefer_inkernel);
     P.tt = ceil_div(NB, kRelayoutPx);
     if (gather && !lists) {
@@ -1141,6 +1153,45 @@ int rroi_align_forward_layout_hip(const float* features, int feature_layout, int
 // image index is >= batch_size are sampled from the NCHW tensor by extra blocks of the prologue launch and left alone
 // by the gather; its direct kernels get no batch count (-1) and write con_idx where P.con_idx.
 extern "C++" {   // (templates)
+// The forward prologue launch (relayout to the chunk-major copy + affine table [+ ROI sort, + the launcher's rest blocks]):
+// shared by the dense two-launch plan and the bucketed one (which runs it unchanged: one group, no launcher).
+template <class T>
+static int launch_forward_prologue(const T* features, const Workspace& ws, bool zero_copy, int groups, bool launcher_rest,
+                                   T* top_data, int batch_size, int num_rois, int height, int width, int channels,
+                                   int pooled_height, int pooled_width, const float* rois, float spatial_scale, int trig,
+                                   int nchunks, hipStream_t stream)
+{
+    constexpr bool kF32 = std::is_same<T, float>::value;
+    const int HW = height * width;
+    const int pitch = row_pitch(width);
+    const int ptiles = ceil_div(HW, kRelayoutPx);
+    const int relayout_tiles = zero_copy ? 0 : ptiles * nchunks * batch_size;
+    // ~3 resident blocks per CU, each streaming several tiles with the next tile prefetched
+    int relayout_blocks = relayout_tiles;
+    if (groups > 1) relayout_blocks = (relayout_blocks + 7) / 8 * 8;   // whole XCD rounds (a block without a tile leaves)
+    if (relayout_blocks > num_cus() * g_tune.prologue_blocks_per_cu) {
+        relayout_blocks = num_cus() * g_tune.prologue_blocks_per_cu;
+        long unit = nchunks;
+        while (unit % 8) unit += nchunks;  // lcm(nchunks, 8): keeps block -> chunk -> XCD stable
+        if (relayout_blocks >= unit) relayout_blocks = (int)(relayout_blocks / unit * unit);
+    }
+    const int aff_blocks = ceil_div(num_rois, 256);
+    const int rest_blocks = launcher_rest ? num_rois : 0;
+    float* rest_out = nullptr;   // (the launcher: fp32)
+    if constexpr (kF32) rest_out = launcher_rest ? top_data : nullptr;
+#define RROI_LAUNCH_PRO(AUX)                                                                        \
+    hipLaunchKernelGGL((rroi_prologue_kernel<AUX, T>),                                                \
+                   dim3(relayout_blocks + aff_blocks + (groups > 1 ? 1 : 0) + rest_blocks), dim3(256), 0, \
+                   stream, features, ws.cm, channels, HW, width, pitch,                           \
+                   make_fastdiv((unsigned)width), nchunks, ptiles, relayout_blocks,               \
+                   relayout_tiles, batch_size, rois, num_rois, pooled_height,                     \
+                   spatial_scale, trig, ws.aff, aff_blocks, rest_out,                             \
+                   pooled_width, groups, ws.sort_rank, ws.sort_order)
+    RROI_LAUNCH_PRO(0);   // plain stores: the copy stays in the L2s that wrote it (write-through: 1.8 us faster alone, the step is not)
+#undef RROI_LAUNCH_PRO
+    return launch_status();
+}
+
 // T: the element type of the map and the crops (float, bf16_t, fp16_t; the plan of a 16-bit call has no fused form, no
 // zero copy and no launcher)
 template <class T>
@@ -1213,32 +1264,9 @@ static int launch_forward(const FwdDispatch& P, const T* features, int feature_l
 
     // prologue: relayout + affine table in one launch
     if (stages & RROI_STAGE_PROLOGUE) {
-        const int ptiles = ceil_div(HW, kRelayoutPx);
-        const int relayout_tiles = zero_copy ? 0 : ptiles * nchunks * batch_size;
-        // ~3 resident blocks per CU, each streaming several tiles with the next tile prefetched
-        int relayout_blocks = relayout_tiles;
-        if (groups > 1) relayout_blocks = (relayout_blocks + 7) / 8 * 8;   // whole XCD rounds (a block without a tile leaves)
-        if (relayout_blocks > num_cus() * g_tune.prologue_blocks_per_cu) {
-            relayout_blocks = num_cus() * g_tune.prologue_blocks_per_cu;
-            long unit = nchunks;
-            while (unit % 8) unit += nchunks;  // lcm(nchunks, 8): keeps block -> chunk -> XCD stable
-            if (relayout_blocks >= unit) relayout_blocks = (int)(relayout_blocks / unit * unit);
-        }
-        const int aff_blocks = ceil_div(num_rois, 256);
-        const int rest_blocks = launcher_rest ? num_rois : 0;
-        float* rest_out = nullptr;   // (the launcher: fp32)
-        if constexpr (kF32) rest_out = launcher_rest ? top_data : nullptr;
-#define RROI_LAUNCH_PRO(AUX)                                                                        \
-    hipLaunchKernelGGL((rroi_prologue_kernel<AUX, T>),                                                \
-                       dim3(relayout_blocks + aff_blocks + (groups > 1 ? 1 : 0) + rest_blocks), dim3(256), 0, \
-                       stream, features, ws.cm, channels, HW, width, pitch,                           \
-                       make_fastdiv((unsigned)width), nchunks, ptiles, relayout_blocks,               \
-                       relayout_tiles, batch_size, rois, num_rois, pooled_height,                     \
-                       spatial_scale, trig, ws.aff, aff_blocks, rest_out,                             \
-                       pooled_width, groups, ws.sort_rank, ws.sort_order)
-        RROI_LAUNCH_PRO(0);   // plain stores: the copy stays in the L2s that wrote it (write-through: 1.8 us faster alone, the step is not)
-#undef RROI_LAUNCH_PRO
-        const int st = launch_status();
+        const int st = launch_forward_prologue(features, ws, zero_copy, groups, launcher_rest, top_data, batch_size, num_rois,
+                                               height, width, channels, pooled_height, pooled_width, rois, spatial_scale, trig,
+                                               nchunks, stream);
         if (st != 1) return st;
     }
     if (stages & RROI_STAGE_GATHER) {
@@ -1367,7 +1395,8 @@ extern "C++" {   // (templates)
 template <class T>
 static int launch_backward(const BwdDispatch& P, const T* top_diff, float spatial_scale, int batch_size, int num_rois,
                            int height, int width, int channels, int pooled_height, int pooled_width, const float* rois,
-                           T* bottom_diff, void* workspace, size_t workspace_bytes, hipStream_t stream)
+                           T* bottom_diff, void* workspace, size_t workspace_bytes, hipStream_t stream,
+                           const CropRow* ragged = nullptr)   // the bucketed call: the gradient crops' table (top_diff is NULL)
 {
     constexpr bool kF32 = std::is_same<T, float>::value;
     const int trig = P.trig;
@@ -1403,6 +1432,9 @@ static int launch_backward(const BwdDispatch& P, const T* top_diff, float spatia
     const BwdWorkspace ws = carve_bwd(workspace, batch_size, channels, height, width, num_rois, NB);
     if (!workspace || workspace_bytes < ws.bytes) return 0;
     if (!kF32 && (P.family == RROI_PLAN_BWD_ATOMIC || td_nhwc || accumulate)) return 0;
+    if (ragged && (td_nhwc || accumulate || !(P.family == RROI_PLAN_BWD_LISTS || P.family == RROI_PLAN_BWD_BUCKETS ||
+                                               P.family == RROI_PLAN_BWD_ORDERED)))
+        return 0;
     // where the gather reads top_diff: the relaid-out fp32 copy, or an fp32 channels-last top_diff in place
     const float* srcT = ws.tdT;
     if constexpr (kF32) srcT = td_nhwc ? top_diff : ws.tdT;
@@ -1505,12 +1537,17 @@ static int launch_backward(const BwdDispatch& P, const T* top_diff, float spatia
             const long cap = (long)num_cus() * 8;
             return n / unit <= cap ? n / unit : cap;
         };
-#define RROI_LAUNCH_PR(FILL, SAUX, BLOCKS, T0, T1)                                                   \
-    hipLaunchKernelGGL((rroi_bwd_pairs_relayout_kernel<FILL, SAUX, T>), dim3((unsigned)(pblocks + (BLOCKS))), \
+#define RROI_LAUNCH_PR_(FILL, SAUX, RAGGED, SRC, BLOCKS, T0, T1)                                     \
+    hipLaunchKernelGGL((rroi_bwd_pairs_relayout_kernel<FILL, SAUX, T, RAGGED>), dim3((unsigned)(pblocks + (BLOCKS))), \
                        dim3(256), 0, stream, ws.aff, num_rois, height, width, pooled_width, NB,          \
                        batch_size, lines_per_roi, dnb, dpw, KL, ws.cnt, ws.off, ws.bsum, ws.pairs,       \
-                       pblocks, top_diff, ws.tdT, channels, nchunks, tt, (int)(BLOCKS), (int)(T0), (int)(T1),            \
+                       pblocks, SRC, ws.tdT, channels, nchunks, tt, (int)(BLOCKS), (int)(T0), (int)(T1),            \
                        ws.scan_blocks, raw_bsum, BL, (g_tune.bwd_skip_dead ? 1 : 0) | (aggregate ? 2 : 0))
+#define RROI_LAUNCH_PR(FILL, SAUX, BLOCKS, T0, T1)                                  \
+    do {                                                                            \
+        if (ragged) RROI_LAUNCH_PR_(FILL, SAUX, true, ragged, BLOCKS, T0, T1);      \
+        else RROI_LAUNCH_PR_(FILL, SAUX, false, top_diff, BLOCKS, T0, T1);          \
+    } while (0)
         if (buckets) {
             // ONE launch: every pair into its pixel's bucket (or overflow chain) || the whole relayout
             const long blocks = relayout_grid(tiles);
@@ -1529,6 +1566,7 @@ static int launch_backward(const BwdDispatch& P, const T* top_diff, float spatia
         }
         }
 #undef RROI_LAUNCH_PR
+#undef RROI_LAUNCH_PR_
         st = launch_status();
         if (st != 1) return st;
         // (3) gather: one thread group per key, no grid-stride
@@ -1964,6 +2002,178 @@ int rroi_align_backward_plan_typed(int dtype, int top_diff_layout, int bottom_di
               P.family == RROI_PLAN_BWD_BUCKETS ? (int)P.ws.kshift : 0, lists ? P.raw_bsum : -1, lists ? (int)P.gy : 0,
               P.dest, P.accumulate && P.family != RROI_PLAN_NONE, P.vec4);
     return 1;
+}
+
+// ------------------------------------------------------------------------------------
+// Bucketed RoIRotate (header section 2b): one pooled width per ROI, one launch chain per call.
+// ------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// What a bucketed forward launches.  The host cannot see the table, so the choice goes by what the caller states:
+// the sum of the widths (the call's real output size), a common divisor of the widths and the crops' alignment.
+FwdDispatch plan_forward_bucketed(int dtype, int batch_size, int num_rois, int height, int width, int channels,
+                                  int pooled_height, int max_pooled_width, long long sum_pooled_widths, int width_multiple,
+                                  int crop_alignment, int path)
+{
+    FwdDispatch P;
+    if (!dtype_ok(dtype)) return P;
+    if (path & ~(0xff | RROI_PATH_TRIG_FP32)) return P;
+    P.trig = (path & RROI_PATH_TRIG_FP32) ? RROI_TRIG_FP32 : RROI_TRIG_DOUBLE;
+    path &= 0xff;
+    if (path != RROI_PATH_AUTO && path != RROI_PATH_DIRECT && path != RROI_PATH_TILED) return P;
+    if (!shape_ok(batch_size, num_rois, height, width, channels, pooled_height, max_pooled_width)) return P;
+    if (width_multiple < 1 || crop_alignment < 1 || sum_pooled_widths < 0) return P;
+    if (num_rois == 0) {
+        P.status = 1;
+        return P;
+    }
+    if (sum_pooled_widths < num_rois || sum_pooled_widths > (long long)num_rois * max_pooled_width) return P;
+    P.nchunks = ceil_div(channels, kChunk);
+    // the ragged gather's contract: every crop's rows are whole 64-byte sectors and every crop starts on one
+    const bool fast_ok = ((long long)pooled_height * width_multiple) % 16 == 0 && crop_alignment % 64 == 0;
+    const double out_elems = (double)channels * pooled_height * (double)sum_pooled_widths;
+    const double map_elems = (double)batch_size * channels * height * width;
+    const bool tiled = path == RROI_PATH_TILED ||
+                       (path == RROI_PATH_AUTO && fast_ok && out_elems >= g_tune.fwd_tiled_min_elems && out_elems >= map_elems / 4);
+    if (tiled && !fast_ok) return P;
+    if (!tiled) {
+        // the ragged patch kernel, at any R: the floor for every width set and address (no thread-per-bin form)
+        if (!plan_patch_forward(num_rois, channels, width, pooled_height, max_pooled_width, P.patch)) return P;
+        P.family = RROI_PLAN_FWD_DIRECT_K2P;
+        P.status = 1;
+        return P;
+    }
+    const int ntiles = ceil_div((long)pooled_height * max_pooled_width, kTileBins);   // the item space: ROI x tiles of the widest
+    if ((long)num_rois * ntiles >= (1L << 31)) return P;
+    // ... of which about ceil(PH * W_i / 64) per ROI exist: the grid is sized for those
+    const long items = std::min<long>((long)num_rois * ntiles,
+                                      (long)(((long long)pooled_height * sum_pooled_widths + kTileBins - 1) / kTileBins) + num_rois);
+    P.gather = {FwdKernel::kStrided, tiled_grid(items, P.nchunks, g_tune.split_wgs_per_cu), ntiles, g_tune.fwd_dbg & ~0xe0};
+    P.groups = 1;
+    P.family = RROI_PLAN_FWD_TWO_LAUNCH;
+    P.status = 1;
+    return P;
+}
+
+template <class T>
+int launch_forward_bucketed(const FwdDispatch& P, const T* features, float spatial_scale, int batch_size, int num_rois,
+                            int height, int width, int channels, int pooled_height, int max_pooled_width, const float* rois,
+                            const CropRow* crops, void* workspace, size_t workspace_bytes, hipStream_t stream)
+{
+    if (P.family == RROI_PLAN_FWD_DIRECT_K2P) {
+        const PatchPlan& p = P.patch;
+        hipLaunchKernelGGL((rroi_fwd_patch_kernel<4, false, T, true>), p.grid, dim3(256), 0, stream, features, rois, crops,
+                           num_rois, channels, height, width, pooled_height, max_pooled_width, spatial_scale, P.trig, batch_size,
+                           p.cw, p.npx, p.npatches, p.prows, p.pcols, (float*)nullptr, (float*)nullptr);
+        return launch_status();
+    }
+    if (P.family != RROI_PLAN_FWD_TWO_LAUNCH) return 0;
+    const Workspace ws = carve(workspace, batch_size, channels, height, width, num_rois, RROI_LAYOUT_NCHW);
+    if (!workspace || workspace_bytes < ws.bytes) return 0;
+    const int nchunks = P.nchunks;
+    const int st = launch_forward_prologue(features, ws, false, 1, false, (T*)nullptr, batch_size, num_rois, height, width,
+                                           channels, pooled_height, max_pooled_width, rois, spatial_scale, P.trig, nchunks, stream);
+    if (st != 1) return st;
+    const int pitch = row_pitch(width);
+    SliceLayout lay;
+    lay.px_bytes = kLineBytes;
+    lay.row_bytes = (unsigned)pitch * kLineBytes;
+    lay.slice_bytes = (unsigned)height * lay.row_bytes;
+    lay.chunk_stride = ((unsigned)height * (unsigned)pitch + 1u) * kChunk;
+    lay.img_stride = lay.chunk_stride * (unsigned)nchunks;
+    const ForwardPlan& plan = P.gather;
+    const FastDiv dt = make_fastdiv((unsigned)plan.ntiles), dp = make_fastdiv((unsigned)max_pooled_width);
+    hipLaunchKernelGGL((rroi_fwd_split_kernel<true, 0, 6, 3, false, 0, false, -1, T, true>), dim3(plan.grid), dim3(2 * kWave), 0,
+                       stream, ws.cm, ws.aff, crops, num_rois, channels, height, width, max_pooled_width,
+                       pooled_height * max_pooled_width, batch_size, nchunks, plan.ntiles, lay, dt, dp, plan.dbg,
+                       XcdGroups{1, nullptr}, RoiSource{nullptr, 0, 0.0f, 0});
+    return launch_status();
+}
+}  // namespace
+extern "C" {
+
+size_t rroi_align_forward_bucketed_workspace_bytes(int batch_size, int channels, int height, int width, int num_rois)
+{
+    return rroi_align_forward_workspace_bytes(batch_size, channels, height, width, num_rois, RROI_LAYOUT_NCHW);
+}
+
+size_t rroi_align_backward_bucketed_workspace_bytes(int batch_size, int channels, int height, int width, int num_rois,
+                                                    int pooled_height, int max_pooled_width)
+{
+    return rroi_align_backward_workspace_bytes(batch_size, channels, height, width, num_rois, pooled_height, max_pooled_width);
+}
+
+int rroi_align_forward_bucketed_plan(int dtype, int batch_size, int num_rois, int height, int width, int channels,
+                                     int pooled_height, int max_pooled_width, long long sum_pooled_widths, int width_multiple,
+                                     int crop_alignment, int path, rroi_align_plan* plan)
+{
+    if (!plan) return 0;
+    const FwdDispatch P = plan_forward_bucketed(dtype, batch_size, num_rois, height, width, channels, pooled_height,
+                                                max_pooled_width, sum_pooled_widths, width_multiple, crop_alignment, path);
+    if (!P.status) return 0;
+    const bool gathers = P.family == RROI_PLAN_FWD_TWO_LAUNCH;
+    fill_plan(plan, P.family, gathers ? RROI_PLAN_KERNEL_STRIDED_RAGGED : -1, P.family == RROI_PLAN_NONE ? 0 : 1,
+              gathers ? P.gather.ntiles : 0,
+              gathers ? dim3(P.gather.grid) : P.family == RROI_PLAN_FWD_DIRECT_K2P ? P.patch.grid : dim3(0, 0, 0), false, false, 0,
+              0, -1, 0, RROI_PLAN_DST_NONE, false, false);
+    return 1;
+}
+
+int rroi_align_backward_bucketed_plan(int dtype, int bottom_diff_layout, int batch_size, int num_rois, int height, int width,
+                                      int channels, int pooled_height, int max_pooled_width, int path, rroi_align_plan* plan)
+{
+    if (!plan) return 0;
+    const BwdDispatch P = plan_backward(RROI_LAYOUT_NCHW, bottom_diff_layout, batch_size, num_rois, height, width, channels,
+                                        pooled_height, max_pooled_width, path, RROI_CALLER_NATIVE, dtype, /*ragged*/ true);
+    if (!P.status) return 0;
+    const bool lists = P.family != RROI_PLAN_NONE;
+    fill_plan(plan, P.family, -1, 0, 0, lists ? P.grid : dim3(0, 0, 0), false, false, 0,
+              P.family == RROI_PLAN_BWD_BUCKETS ? (int)P.ws.kshift : 0, lists ? P.raw_bsum : -1, lists ? (int)P.gy : 0, P.dest,
+              false, false);
+    return 1;
+}
+
+int rroi_align_forward_bucketed_hip(const void* features, int dtype, float spatial_scale, int batch_size, int num_rois,
+                                    int height, int width, int channels, int pooled_height, int max_pooled_width,
+                                    long long sum_pooled_widths, int width_multiple, int crop_alignment, const float* rois,
+                                    const rroi_align_crop* crops, void* workspace, size_t workspace_bytes, int path,
+                                    void* stream_)
+{
+    static_assert(sizeof(rroi_align_crop) == sizeof(CropRow), "the table's row");
+    const FwdDispatch P = plan_forward_bucketed(dtype, batch_size, num_rois, height, width, channels, pooled_height,
+                                                max_pooled_width, sum_pooled_widths, width_multiple, crop_alignment, path);
+    if (!P.status) return 0;
+    if (P.family == RROI_PLAN_NONE) return 1;
+    if (!features || !rois || !crops) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const CropRow* table = reinterpret_cast<const CropRow*>(crops);
+    auto run = [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_forward_bucketed(P, static_cast<const T*>(features), spatial_scale, batch_size, num_rois, height, width,
+                                       channels, pooled_height, max_pooled_width, rois, table, workspace, workspace_bytes, stream);
+    };
+    return dtype == RROI_DTYPE_BF16 ? run(bf16_t{}) : dtype == RROI_DTYPE_FP16 ? run(fp16_t{}) : run(float{});
+}
+
+int rroi_align_backward_bucketed_hip(const rroi_align_crop* top_diffs, int dtype, int bottom_diff_layout, float spatial_scale,
+                                     int batch_size, int num_rois, int height, int width, int channels, int pooled_height,
+                                     int max_pooled_width, const float* rois, void* bottom_diff, void* workspace,
+                                     size_t workspace_bytes, int path, void* stream_)
+{
+    const BwdDispatch P = plan_backward(RROI_LAYOUT_NCHW, bottom_diff_layout, batch_size, num_rois, height, width, channels,
+                                        pooled_height, max_pooled_width, path, RROI_CALLER_NATIVE, dtype, /*ragged*/ true);
+    if (!P.status) return 0;
+    if (!bottom_diff) return 0;
+    if (P.family != RROI_PLAN_NONE && (!top_diffs || !rois)) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const CropRow* table = reinterpret_cast<const CropRow*>(top_diffs);
+    auto run = [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_backward(P, static_cast<const T*>(nullptr), spatial_scale, batch_size, num_rois, height, width, channels,
+                               pooled_height, max_pooled_width, rois, static_cast<T*>(bottom_diff), workspace, workspace_bytes,
+                               stream, table);
+    };
+    return dtype == RROI_DTYPE_BF16 ? run(bf16_t{}) : dtype == RROI_DTYPE_FP16 ? run(fp16_t{}) : run(float{});
 }
 
 int rroi_align_set_trig_recipe_hip(int recipe) { return recipe == RROI_TRIG_DOUBLE ? 1 : 0; }   // deprecated shim, see the header

@@ -181,13 +181,16 @@ __device__ __forceinline__ void pairs_reserve_wave(unsigned* __restrict__ tab, c
 // the key's segment (fill pass, after the scan).  MODE 2 (round 3): ONE pass -- cnt[key]++ hands out the
 // slots of a fixed-capacity bucket per pixel (a few times the average list), the rare pair beyond it is
 // chained into the overflow array: no count pass, no scan, and the relayout of top_diff is one launch.
-template <int MODE>
+// RAGGED (the bucketed backward): `pooled_width` is the call's largest width (bins are indexed in that grid) and ROI n
+// has the bins pw < ragged[n].pooled_width only -- none at all when the row is skipped.
+template <int MODE, bool RAGGED = false>
 __device__ __forceinline__ void pairs_body(unsigned idx, const Affine* __restrict__ aff, int num_rois,
                                            int height, int width, int pooled_height, int pooled_width, int batch_size,
                                            unsigned lines_per_roi, const PatchMap& pm,
                                            const KeyLayout& L, int* __restrict__ cnt,
                                            const unsigned* __restrict__ off, const unsigned* __restrict__ bsum,
-                                           uint2* __restrict__ pairs, const BucketLists& bl, unsigned* __restrict__ agg = nullptr)
+                                           uint2* __restrict__ pairs, const BucketLists& bl, unsigned* __restrict__ agg = nullptr,
+                                           const CropRow* __restrict__ ragged = nullptr)
 {
     constexpr bool FILL = MODE == 1;
     // (the lanes of a wave share the ROI and the patch: idx is a multiple of 64 plus the lane, the total a multiple of 64)
@@ -197,7 +200,14 @@ __device__ __forceinline__ void pairs_body(unsigned idx, const Affine* __restric
     const unsigned py = fdiv(patch, pm.div_npx), px = patch - py * pm.npx;
     const unsigned ph = py * (64u >> pm.pc_shift) + (l >> pm.pc_shift);
     const unsigned pw = (px << pm.pc_shift) + (l & ((1u << pm.pc_shift) - 1u));
-    const bool has_bin = n < (unsigned)num_rois && ph < (unsigned)pooled_height && pw < (unsigned)pooled_width;
+    unsigned roi_width = (unsigned)pooled_width;
+    if constexpr (RAGGED) {   // (n < num_rois: idx < num_rois * lanes_per_roi; a wave's lanes share the ROI)
+        unsigned long long base;
+        int wn;
+        crop_row(ragged, n, pooled_width, base, wn);
+        roi_width = (unsigned)wn;
+    }
+    const bool has_bin = n < (unsigned)num_rois && ph < (unsigned)pooled_height && pw < roi_width;
     const unsigned j = ph * (unsigned)pooled_width + pw;
     if (MODE == 2 && !agg) {
         // few patches per wave: one returning atomic per pair as it is found, no table to set up
@@ -263,25 +273,33 @@ __device__ __forceinline__ void pairs_body(unsigned idx, const Affine* __restric
 // [tile_begin, tile_end) of top_diff -- bound by HBM.  They share the chip instead of running
 // one after the other; the host gives each of the two launches half of the tiles.
 // TS: the element type of the caller's top_diff (the copy is fp32)
-template <int MODE, int SAUX, class TS = float>
+// RAGGED: `top_diff_` is the table of the per-ROI gradient crops; pooled_width / NB are the call's largest.
+// The lists and the copy keep the dense (roi, bin of PH x pooled_width) indexing, so every consumer is unchanged.
+template <int MODE, int SAUX, class TS = float, bool RAGGED = false>
 __global__ __launch_bounds__(256, 7) void rroi_bwd_pairs_relayout_kernel(   // (seven workgroups per CU: <= 72 VGPRs, as in rounds 3-4)
     const Affine* __restrict__ aff, int num_rois, int height, int width, int pooled_width, int NB,
     int batch_size, unsigned lines_per_roi, PatchMap pm, FastDiv div_pw, KeyLayout L,
     int* __restrict__ cnt, const unsigned* __restrict__ off, const unsigned* __restrict__ bsum,
-    uint2* __restrict__ pairs, int pair_blocks, const TS* __restrict__ top_diff,
+    uint2* __restrict__ pairs, int pair_blocks,
+    typename std::conditional<RAGGED, const CropRow*, const TS*>::type __restrict__ top_diff_,
     float* __restrict__ tdT, int C, int nchunks, int ptiles, int relayout_blocks, int tile_begin,
     int tile_end, unsigned scan_blocks, int raw_bsum, BucketLists bl = BucketLists{0u, nullptr, nullptr, nullptr},
     int skip_dead_bins = 1)   // flags: bit 0 dead bins are not copied, bit 1 the pair blocks aggregate their reservations per wave
 {
     __shared__ __attribute__((aligned(16))) float T[kChunk * kTP];
     static_assert(4 * kAggWords <= kChunk * kTP, "the four waves' aggregation tables live in the relayout tile");
+    const TS* top_diff = nullptr;
+    const CropRow* ragged = nullptr;
+    if constexpr (RAGGED) ragged = top_diff_;
+    else top_diff = top_diff_;
     if ((int)blockIdx.x < pair_blocks) {
         if (MODE == 1) bsum = block_prefix(bsum, scan_blocks, raw_bsum != 0, reinterpret_cast<unsigned*>(T));
         const unsigned total = (unsigned)num_rois * pm.lanes_per_roi;
         for (unsigned idx = blockIdx.x * 256u + threadIdx.x; idx < total; idx += (unsigned)pair_blocks * 256u)
-            pairs_body<MODE>(idx, aff, num_rois, height, width, NB / pooled_width, pooled_width, batch_size,
+            pairs_body<MODE, RAGGED>(idx, aff, num_rois, height, width, NB / pooled_width, pooled_width, batch_size,
                              lines_per_roi, pm, L, cnt, off, bsum, pairs, bl,
-                             (skip_dead_bins & 2) ? reinterpret_cast<unsigned*>(T) + (threadIdx.x >> 6) * kAggWords : nullptr);
+                             (skip_dead_bins & 2) ? reinterpret_cast<unsigned*>(T) + (threadIdx.x >> 6) * kAggWords : nullptr,
+                             ragged);
         return;
     }
     // block j takes the pixel ranges j, j + blocks, ... of [tile_begin, tile_end), all chunks of each
@@ -292,9 +310,10 @@ __global__ __launch_bounds__(256, 7) void rroi_bwd_pairs_relayout_kernel(   // (
         bin_pairs(aff[n], ph, pw, height, width, batch_size, L, [&](unsigned, float) { any = true; });
         return any;
     };
-    relayout_run<SAUX, true, true>(T, top_diff, tdT, C, NB, pooled_width, pooled_width, div_pw, nchunks, ptiles,
+    relayout_run<SAUX, true, true, decltype(live_bin), TS, RAGGED>(
+                          T, top_diff, tdT, C, NB, pooled_width, pooled_width, div_pw, nchunks, ptiles,
                           tile_begin + ((int)blockIdx.x - pair_blocks) * nchunks, relayout_blocks * nchunks, tile_end,
-                          aff, batch_size, live_bin);
+                          aff, batch_size, live_bin, ragged);
 }
 
 // Exclusive scan of cnt[0..N) (N = keys + 1, the last element reads as 0), two levels:

@@ -227,6 +227,31 @@ struct SliceLayout {
     unsigned img_stride;    // floats  (fits: shape_ok bounds it)
 };
 
+// ------------------------------------------------------------------------------------
+// Bucketed (ragged) calls, DESIGN 5.9: one row of the caller's DEVICE table per ROI -- the address of the ROI's own dense
+// (C, PH, W_i) crop and its pooled width W_i (include/rroi_align_hip.h: rroi_align_crop, 16 bytes).  A kernel reads a row
+// into SCALARS (readfirstlane): the crop's buffer descriptor and every loop bound derive from it, and a descriptor that
+// derives from a VGPR puts each load or store into a waterfall loop.  A row the host could not check -- a width outside
+// [1, max_width], a null address -- reads as width 0: the ROI is skipped, nothing of it is read or written.
+// ------------------------------------------------------------------------------------
+struct CropRow {
+    unsigned long long data;
+    int pooled_width;
+    int reserved;
+};
+static_assert(sizeof(CropRow) == 16, "rroi_align_crop is one 16-byte row");
+
+__device__ __forceinline__ void crop_row(const CropRow* __restrict__ table, unsigned n, int max_width,
+                                         unsigned long long& base, int& w)
+{
+    const CropRow r = table[n];
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)r.data);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(r.data >> 32));
+    base = ((unsigned long long)hi << 32) | lo;
+    w = __builtin_amdgcn_readfirstlane(r.pooled_width);
+    if (w < 1 || w > max_width || base == 0ull) w = 0;
+}
+
 // Buffer addressing: every tap load and every output store goes through a raw buffer
 // descriptor (base, num_records) whose range check does the predication in hardware -- a lane
 // whose byte offset is >= num_records reads zeros / stores nothing and costs no memory access.

@@ -33,14 +33,20 @@ constexpr int kTP = kRelayoutPx + 4;
 // reads the 8 chunks of a bin together, and eight lines of one DRAM page cost less than eight lines 65 KB
 // apart (cfg3: gather 52 -> 39 us).
 // TS: the element type of the source (the caller's tensor); the copy is fp32 whatever it is.
-template <int AUX, bool MASK, bool PIXMAJOR = false, class Live = NoLive, class TS = float>
+// RAGGED (the bucketed backward; with MASK and PIXMAJOR): the source is not one tensor but a crop per "image":
+// element (c, y, x) of image b is at ragged[b].data + (c * PH + y) * W_b + x, and columns x >= W_b do not exist -- they
+// are treated like masked bins, never read and never written; `width` is the call's largest width (the copy's).  Where
+// the call's width, W_b and the crop's address are all multiples of four elements a lane's four pixels are one vector
+// load, as in the dense form; any other crop is read element by element.
+template <int AUX, bool MASK, bool PIXMAJOR = false, class Live = NoLive, class TS = float, bool RAGGED = false>
 __device__ __forceinline__ void relayout_run(float* __restrict__ T, const TS* __restrict__ nchw,
                                                float* __restrict__ cm, int C, int HW, int width, int pitch,
                                                FastDiv div_w, int nchunks, int ptiles, int first_tile,
                                                int tile_stride, int relayout_tiles,
                                                const Affine* __restrict__ mask_aff, int mask_batches,
-                                               Live is_live = Live{})
+                                               Live is_live = Live{}, const CropRow* __restrict__ ragged = nullptr)
 {
+    static_assert(!RAGGED || (MASK && PIXMAJOR), "RAGGED: the backward's relayout of top_diff");
     constexpr bool LIVE = !std::is_same<Live, NoLive>::value;
     static_assert(!LIVE || PIXMAJOR, "the predicate is evaluated once per pixel range, on its first chunk");
     // (LIVE) one bit per pixel of a 128-pixel range, evaluated by every wave for itself on the range's first chunk
@@ -63,7 +69,14 @@ __device__ __forceinline__ void relayout_run(float* __restrict__ T, const TS* __
     // (MASK) highest live pooled column of image b: pw <= rpw  <=>  pw <= floor(rpw) for integer pw
     auto live_limit = [&](int b) -> float {
         const Affine A = mask_aff[b];
-        return (A.batch >= 0 && A.batch < mask_batches) ? A.rpw : -1.0f;
+        float lim = (A.batch >= 0 && A.batch < mask_batches) ? A.rpw : -1.0f;
+        if constexpr (RAGGED) {   // ... and the crop's last column (a skipped row has width 0: nothing is live)
+            unsigned long long base;
+            int wb;
+            crop_row(ragged, (unsigned)b, width, base, wb);
+            if (!(lim < (float)(wb - 1))) lim = (float)(wb - 1);
+        }
+        return lim;
     };
 
     // the tile in flight is kept in the SOURCE's type and widened where it goes into LDS: a conversion right behind the
@@ -99,6 +112,40 @@ __device__ __forceinline__ void relayout_run(float* __restrict__ T, const TS* __
                 const unsigned long long half = x4 < 16 ? next_lo : next_hi;
                 live = live && ((half >> (4 * (x4 & 15))) & 0xFull) != 0ull;
             }
+        }
+        if constexpr (RAGGED) {
+            unsigned long long base;
+            int wb;
+            crop_row(ragged, (unsigned)b, width, base, wb);
+            const unsigned gp = (unsigned)(p0 + p);
+            // the lane's four pixels in the call's (PH, width) grid
+            unsigned ey[4], ex[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                ey[e] = fdiv(gp + (unsigned)e, div_w);
+                ex[e] = gp + (unsigned)e - ey[e] * (unsigned)width;
+            }
+            const bool rvec = (width & 3) == 0 && (wb & 3) == 0 && (base & (4 * sizeof(TS) - 1)) == 0;   // (wave-uniform)
+            const size_t plane = (size_t)(HW / width) * (size_t)wb;   // PH * W_b elements per channel of the crop
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = w * 8 + i * 2 + csub;
+                vraw v = {0, 0, 0, 0};
+                if (c0 + c < C && live && wb > 0) {
+                    const TS* cb = reinterpret_cast<const TS*>(base) + (size_t)(c0 + c) * plane;
+                    if (rvec) {   // one row, x % 4 == 0: all four columns are inside the crop or none is
+                        if (gp < (unsigned)HW && ex[0] < (unsigned)wb)
+                            v = __builtin_nontemporal_load(reinterpret_cast<const vraw*>(cb + (size_t)ey[0] * wb + ex[0]));
+                    } else {
+                        if (gp + 0u < (unsigned)HW && ex[0] < (unsigned)wb) v.x = cb[(size_t)ey[0] * wb + ex[0]];
+                        if (gp + 1u < (unsigned)HW && ex[1] < (unsigned)wb) v.y = cb[(size_t)ey[1] * wb + ex[1]];
+                        if (gp + 2u < (unsigned)HW && ex[2] < (unsigned)wb) v.z = cb[(size_t)ey[2] * wb + ex[2]];
+                        if (gp + 3u < (unsigned)HW && ex[3] < (unsigned)wb) v.w = cb[(size_t)ey[3] * wb + ex[3]];
+                    }
+                }
+                r[i] = v;
+            }
+            return;
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -443,10 +490,18 @@ struct RoiSource {   // NCHW_SRC: where the storer takes its affines from
     float spatial_scale;
     int trig;
 };
+// RAGGED (the bucketed call with many ROIs): the strided form over per-ROI crops.  `out_` is the crop table,
+// `pooled_width` / `NB` / `ntiles` are those of the call's LARGEST width (they size the item space: item = ROI * ntiles +
+// tile); ROI i has its own width W_i, ceil(PH * W_i / 64) tiles, bins decoded with W_i, and its own crop as the output
+// descriptor.  An item beyond its ROI's tiles does not exist: the storer's walk steps over it (seek) and tells the gatherer
+// through LDS whether another item follows, so the two waves still meet at two barriers per EXISTING item and neither
+// ever does both loads and stores.  The form's contract -- PH * W_i % 16 == 0, the crop 64-byte aligned -- is checked per
+// row: a row that breaks it (or has a width outside [1, pooled_width]) is skipped.  One group (no XCD groups).
 template <bool VEC_STORE, int EARLY, int OCC, int HID, bool ONHWC, int SHIFT, bool NCHW_SRC = false, int WAUX = -1,
-          class TO = float>
+          class TO = float, bool RAGGED = false>
 __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
-    const float* __restrict__ map, const Affine* __restrict__ aff, TO* __restrict__ out,
+    const float* __restrict__ map, const Affine* __restrict__ aff,
+    typename std::conditional<RAGGED, const CropRow*, TO*>::type __restrict__ out_,
     int num_rois, int C, int height, int width, int pooled_width, int NB, int batch_size,
     int nchunks, int ntiles, SliceLayout lay, FastDiv div_tiles, FastDiv div_pw, int dbg, XcdGroups xg,
     RoiSource roi_src = RoiSource{nullptr, 0, 0.0f, 0})
@@ -494,6 +549,14 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
     __shared__ unsigned char HPbuf[2 * kRecs];
     __shared__ uint4 shead[2];  // per record set: LO groups, HI groups, mask of the bins that are in a group
     __shared__ int sbatch[2];   // ... and the item's image index (the gatherer takes it from here, not from memory)
+    __shared__ unsigned smore[RAGGED ? 2 : 1];   // RAGGED: per record set, 1 = the set holds an item, 0 = the walk has ended
+    static_assert(!RAGGED || (VEC_STORE && !ONHWC && SHIFT == 0 && !NCHW_SRC && WAUX < 0), "RAGGED: the strided NCHW form only");
+    // the dense crops / (RAGGED) the crop table
+    TO* out = nullptr;
+    const CropRow* table = nullptr;
+    if constexpr (RAGGED) table = out_;
+    else out = out_;
+    (void)table;
 
     const unsigned lane = threadIdx.x & 63u;
     // wave 0 gathers (loads only), wave 1 streams the finished tiles out (stores only)
@@ -523,6 +586,27 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
     };
     const unsigned px_bytes = lay.px_bytes;
     const unsigned row_bytes = lay.row_bytes;
+    // RAGGED: the ROI's own width and crop (scalars) and its tiles -- 0 for a row that is skipped
+    const unsigned rg_ph = RAGGED ? (unsigned)NB / (unsigned)pooled_width : 0u;   // the pooled height
+    auto rg_tiles = [&](unsigned n, unsigned& w, unsigned long long& base) -> unsigned {
+        int wi;
+        crop_row(table, n, pooled_width, base, wi);
+        w = (unsigned)wi;
+        if (((rg_ph * w) & 15u) || (base & 63ull)) w = 0u;   // the form's contract: rows of whole sectors, 64-byte aligned crops
+        return (rg_ph * w + (unsigned)kTileBins - 1u) / (unsigned)kTileBins;
+    };
+    // the first EXISTING item at or after c in this slot's sequence (c, c + nslots, ...); kEndItem: none
+    constexpr unsigned kEndItem = 0xffffffffu;
+    auto seek = [&](unsigned c, unsigned& n, unsigned& t, unsigned& w, unsigned long long& base) -> unsigned {
+        for (; c < items; c += nslots) {
+            n = roi_of(c, t);
+            if (t < rg_tiles(n, w, base)) return c;
+        }
+        return kEndItem;
+    };
+    unsigned rg_w = 0u;                                    // width of the item being planned (geometry)
+    unsigned rg_nb_prev = 0u;                              // PH * W_i and crop of the item being drained
+    unsigned long long rg_base_prev = 0ull;
 
     // lane = q + 8*b: the 8 lanes that fetch the 8 channel quads of ONE pixel (one 128-byte
     // line) are consecutive, so the texture addresser merges them into two 64-byte
@@ -560,11 +644,11 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
         // SHIFT: lanes 0..15 are the 16 bins in front of the tile's own 48 (negative for the first tile of a row)
         const int sbin = (int)(t * (unsigned)kOwnBins + lane) - kFront;
         const unsigned bin = (unsigned)max(sbin, 0);
-        const unsigned ph = fdiv(bin, div_pw);
-        const unsigned pw = bin - ph * (unsigned)pooled_width;
+        const unsigned ph = RAGGED ? bin / rg_w : fdiv(bin, div_pw);          // (rg_w >= 1: the item exists)
+        const unsigned pw = bin - ph * (RAGGED ? rg_w : (unsigned)pooled_width);
         float bcx, bcy;
         bool active = bin_centre(A, (int)ph, (int)pw, height, width, bcx, bcy);
-        active = active && sbin >= 0 && bin < (unsigned)NB && batch_ok;
+        active = active && sbin >= 0 && bin < (RAGGED ? rg_ph * rg_w : (unsigned)NB) && batch_ok;
         const float fx = floorf(bcx), fy = floorf(bcy);
         const int x0 = f2i_sat(fx), x1 = f2i_sat(ceilf(bcx));
         const int y0 = f2i_sat(fy), y1 = f2i_sat(ceilf(bcy));
@@ -687,7 +771,7 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
     // phase C, the storer's: the [rows < C] x [64 bins] tile leaves T for its registers between the two
     // barriers, then goes out as 256-byte row segments (dbg & 1, the ablation knob, drops the stores)
     auto drain_tile = [&](unsigned n, unsigned t, unsigned long long cur_mask, bool skip) {
-        if (ONHWC) {
+        if constexpr (ONHWC) {
             // channels-last crops (R, PH*PW, C): lane = (channel quad q, bin b) as in phase B; the tile is read back
             // along its columns (the mapping put() wrote it with), a store covers 8 bins x 128 B
             v4f c[kIters];
@@ -724,6 +808,24 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
         wg_lds_barrier();  // T has been read: the gatherer may blend the next tile into it
         const bool live = !(dbg & 1) && !skip;
         // descriptor over this (roi, chunk) block of the output: rows >= C fall out of range
+        if constexpr (RAGGED) {
+            // ... of the ROI's own crop: PH * W_i bins per channel row, 16-byte stores (the form's contract)
+            const unsigned nb = rg_nb_prev;
+            TO* obase = reinterpret_cast<TO*>(rg_base_prev) + (size_t)(k * kChunk) * nb;
+            const __amdgpu_buffer_rsrc_t ws = make_rsrc(obase, chans_here * nb * kEs);
+            const unsigned bin0 = t * kTileBins + col;
+            const unsigned nib = (unsigned)(cur_mask >> col) & 15u;
+            const bool a0 = nib & 1u, a1 = nib & 2u, a2 = nib & 4u, a3 = nib & 8u;
+#pragma unroll
+            for (int s4 = 0; s4 < kChunk / 4; ++s4) {
+                const unsigned r = s4 * 4 + row0;
+                const unsigned off = (r * nb + bin0) * kEs;
+                const v4f o = {a0 ? v[s4].x : 0.f, a1 ? v[s4].y : 0.f, a2 ? v[s4].z : 0.f, a3 ? v[s4].w : 0.f};
+                if (s4 < kMinorStores) buf_store4<TO, kMinorAux>(ws, (live && bin0 < nb) ? off : kOOB, o);
+                else buf_store4<TO, kStoreAux>(ws, (live && bin0 < nb) ? off : kOOB, o);
+            }
+            return;
+        }
         TO* obase = out + ((size_t)n * C + k * kChunk) * NB;
         const __amdgpu_buffer_rsrc_t ws = make_rsrc(obase, chans_here * (unsigned)NB * kEs);
         const unsigned bin0 = t * kTileBins + col;
@@ -956,10 +1058,15 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
     constexpr unsigned kEnd = 0xffffffffu;
     auto next = [&](unsigned c) -> unsigned { return c + nslots < items ? c + nslots : kEnd; };
     unsigned cur = slot < items ? slot : kEnd;
+    unsigned rg_t0 = 0u, rg_n0 = 0u, rg_w0 = 0u;
+    unsigned long long rg_base0 = 0ull;
+    if constexpr (RAGGED) cur = seek(slot, rg_n0, rg_t0, rg_w0, rg_base0);   // (both waves: the same answer)
     if (cur == kEnd) return;
     if (storer) {
         unsigned t;
         unsigned n = roi_of(cur, t);
+        unsigned long long rg_base = rg_base0;
+        if constexpr (RAGGED) rg_w = rg_w0;
         unsigned p = 0;
         unsigned gl, gh;
         unsigned long long mask_cur = 0, mask_prev = 0;
@@ -975,6 +1082,7 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
             if (lane == 0) {
                 shead[pp] = make_uint4(gl, gh, (unsigned)m, (unsigned)(m >> 32));
                 sbatch[pp] = A.batch;
+                if constexpr (RAGGED) smore[pp] = 1u;
             }
         };
         plan(n, t, 0, mask_cur);
@@ -993,6 +1101,18 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
             t_prev = t;
             mask_prev = mask_cur;
             skip_prev = skip_cur;
+            if constexpr (RAGGED) {
+                rg_nb_prev = rg_ph * rg_w;
+                rg_base_prev = rg_base;
+                cur = seek(cur + nslots, n, t, rg_w, rg_base);
+                if (cur != kEnd) {
+                    p ^= 1u;
+                    plan(n, t, p, mask_cur);
+                } else if (lane == 0) {
+                    smore[p ^ 1u] = 0u;   // the set the gatherer looks at next: no item in it
+                }
+                continue;
+            }
             cur = next(cur);
             if (cur != kEnd) {
                 n = roi_of(cur, t);
@@ -1006,8 +1126,9 @@ __global__ __launch_bounds__(2 * kWave, OCC) void rroi_fwd_split_kernel(
     // not urgent: with the gatherer ahead in the issue arbitration the call is 0.7 us shorter (any level > 0)
     __builtin_amdgcn_s_setprio(2);
     unsigned p = 0;
-    for (;; cur = next(cur), p ^= 1u) {
+    for (;; cur = RAGGED ? cur : next(cur), p ^= 1u) {
         wg_lds_barrier();  // 1: the storer has put this item's records into set p (and our previous tile is complete)
+        if constexpr (RAGGED) cur = __builtin_amdgcn_readfirstlane((int)smore[p]) ? 0u : kEnd;   // the storer's walk says
         if (cur == kEnd) {
             wg_lds_barrier();  // 2
             break;
@@ -1158,9 +1279,14 @@ constexpr unsigned kPairShift = 1u << 20;
 // WITH_IDX: also the reference ABI's con_idx_x / con_idx_y (kernel.cu:144-145); batch_size < 0 = unknown (that ABI): the
 // image index is trusted as the reference trusts it.
 // T: the element type of the map and the crops (a row pair of a 16-bit map is one 4-byte load)
-template <int U, bool WITH_IDX = false, class T = float>
+// RAGGED (the bucketed call's floor: any widths, any element-aligned addresses, any R): `out` is the crop
+// table, `pooled_width` the largest width of the call -- the patch grid is sized for it.  The workgroup reads its ROI's row
+// into scalars; a patch beyond the ROI's own width (or of a skipped row) leaves at once, before the barrier; the crop is
+// the ROI's own dense (C, PH, W_i) block.  The geometry of a bin does not depend on the pooled width (kernel.cu:49-107).
+template <int U, bool WITH_IDX = false, class T = float, bool RAGGED = false>
 __global__ __launch_bounds__(256) void rroi_fwd_patch_kernel(
-    const T* __restrict__ feat, const float* __restrict__ rois, T* __restrict__ out, int num_rois, int C, int height,
+    const T* __restrict__ feat, const float* __restrict__ rois,
+    typename std::conditional<RAGGED, const CropRow*, T*>::type __restrict__ out, int num_rois, int C, int height,
     int width, int pooled_height, int pooled_width, float spatial_scale, int trig, int batch_size, int cwave, int npx,
     int npatches, int prows, int pcols, float* __restrict__ idx_x = nullptr, float* __restrict__ idx_y = nullptr)
 {
@@ -1175,7 +1301,16 @@ __global__ __launch_bounds__(256) void rroi_fwd_patch_kernel(
     // pooled size: 4 x 16 for 11 x 96, 3 x 21 for 11 x 83), lane = row-major position in it
     const int lrow = lane / pcols, lcol = lane - lrow * pcols;
     const int ph = py * prows + lrow, pw = px * pcols + lcol;
-    const bool inside = lrow < prows && ph < pooled_height && pw < pooled_width;
+    int roi_width = pooled_width;   // RAGGED: the ROI's own
+    T* crop = nullptr;
+    if constexpr (RAGGED) {
+        static_assert(!WITH_IDX, "the reference ABI has no bucketed call");
+        unsigned long long base;
+        crop_row(out, (unsigned)n, pooled_width, base, roi_width);
+        if (px * pcols >= roi_width) return;   // (wave-uniform; a skipped row has width 0)
+        crop = reinterpret_cast<T*>(base);
+    }
+    const bool inside = lrow < prows && ph < pooled_height && pw < (RAGGED ? roi_width : pooled_width);
     if (wv == 0) {
         const Affine A = make_affine(rois + (size_t)n * 6, pooled_height, spatial_scale, trig);
         float bcx, bcy;
@@ -1214,12 +1349,19 @@ __global__ __launch_bounds__(256) void rroi_fwd_patch_kernel(
     const bool v00 = f & kV00, v01 = f & kV01, v10 = f & kV10, v11 = f & kV11;
     float wlt, wrt, wrb, wlb;
     tap_weights(r.rx, r.ry, wlt, wrt, wrb, wlb);
-    const int NB = pooled_height * pooled_width;
+    const int NB = pooled_height * (RAGGED ? roi_width : pooled_width);
     const size_t HW = (size_t)height * width;
     const unsigned plane_bytes = (unsigned)(HW * sizeof(T));
     const T* plane = feat + ((size_t)batch * C + c_begin) * HW;
-    const size_t o0 = ((size_t)n * C + c_begin) * NB + (size_t)ph * pooled_width + pw;
-    T* op = out + o0;
+    size_t o0;
+    T* op;
+    if constexpr (RAGGED) {
+        o0 = (size_t)c_begin * NB + (size_t)ph * roi_width + pw;
+        op = crop + o0;
+    } else {
+        o0 = ((size_t)n * C + c_begin) * NB + (size_t)ph * pooled_width + pw;
+        op = out + o0;
+    }
     typedef float v2f __attribute__((ext_vector_type(2)));
     auto pair = [&](const T* pl, unsigned o) -> v2f {
         if constexpr (sizeof(T) == 4) {

@@ -23,7 +23,7 @@ import torch.nn.functional as F
 
 from rroi_align.batched import _crops_channels_last, rois_from_quads
 from rroi_align.decode import ctc_greedy_decode
-from rroi_align.modules.rroi_align import _RRoiAlign
+from rroi_align.modules.rroi_align import _RRoiAlign, _RRoiAlignBucketed
 
 TARGET_H = 11           # tools/ocr_utils.py:147
 SPATIAL_SCALE = 1.0 / 4  # :151, features[1] is the 1/4-resolution map
@@ -76,7 +76,7 @@ def target_widths_host(boxes):
     return (np.maximum(2, gw // 32) * 32).tolist()
 
 
-def batched(net, converter, features, boxes, return_crops=False, gw_host=None, batch_index=None):
+def batched(net, converter, features, boxes, return_crops=False, gw_host=None, batch_index=None, bucketed=False):
     """All words of an image at once.  `boxes`: (N, >= 8) tensor on the device (or array).
     `gw_host`: the boxes' pooled widths when the caller already has them on the host (`infer_image`:
     the boxes come out of the host-side merge: `target_widths_host`) -- then nothing is
@@ -85,7 +85,10 @@ def batched(net, converter, features, boxes, return_crops=False, gw_host=None, b
     crop's, rounded once), the head runs in 16 bits and the greedy CTC reads its 16-bit log-probabilities as they are --
     no widening copy anywhere on the path.  Quads, ROI rows and widths are float32 / int32: they carry geometry.
     `batch_index` (N,): the image each box belongs to when `features` hold SEVERAL images (`infer_batch`) -- the op's
-    own first ROI column (`tools/ocr_utils.py:151` writes 0 there: one image per call); still ONE RoIRotate launch."""
+    own first ROI column (`tools/ocr_utils.py:151` writes 0 there: one image per call); still ONE RoIRotate launch.
+    `bucketed` (opt-in): the crops come from the bucketed op (`_RRoiAlignBucketed`) -- every word pooled at its own
+    bucket's width, each bucket a dense tensor the head takes as it is: no crop tensor at the widest width, no
+    index_select, no slice.  The same crops bit for bit, hence the same texts."""
     focr = features[1]
     quads = torch.as_tensor(boxes, dtype=torch.float32, device=focr.device)[:, :8].contiguous()
     n = quads.shape[0]
@@ -101,14 +104,21 @@ def batched(net, converter, features, boxes, return_crops=False, gw_host=None, b
         if gw_host.numel() != n:
             raise ValueError("gw_host must have one width per box")
     widths = sorted(set(int(v) for v in gw_host))
-    # (the crops follow the features' layout: a channels_last network gets channels_last crops, no relayout on either side)
-    crops_all = _RRoiAlign(TARGET_H, widths[-1], SPATIAL_SCALE, _crops_channels_last(focr, None))(focr, rois)
     texts = [None] * n
     crops, labels = [None] * n, [None] * n
     # every bucket's head and decode are enqueued before anything is read back: one wait for the image,
     # not two per bucket (the buckets' index lists come from the widths that are on the host already)
     pending = []
     gw_list = gw_host.tolist()
+    if bucketed:
+        for idx_dev, x in _RRoiAlignBucketed(TARGET_H, SPATIAL_SCALE)(focr, rois, gw_list):
+            logp = net.forward_ocr(x)
+            decoded, dlen, lab = ctc_greedy_decode(logp, None, return_labels=True)
+            pending.append(([i for i, v in enumerate(gw_list) if int(v) == x.shape[3]], decoded, dlen, x, lab))
+        widths = []
+    else:
+        # (the crops follow the features' layout: a channels_last network gets channels_last crops, no relayout on either side)
+        crops_all = _RRoiAlign(TARGET_H, widths[-1], SPATIAL_SCALE, _crops_channels_last(focr, None))(focr, rois)
     for wdt in widths:                                  # buckets are multiples of 32: a handful
         idx = [i for i, v in enumerate(gw_list) if int(v) == wdt]
         idx_dev = torch.tensor(idx, dtype=torch.int64).to(focr.device, non_blocking=True)
@@ -125,7 +135,7 @@ def batched(net, converter, features, boxes, return_crops=False, gw_host=None, b
     return (texts, crops, labels) if return_crops else texts
 
 
-def infer_image(net, converter, im, detector=None, segm_thresh=0.5, return_debug=False):
+def infer_image(net, converter, im, detector=None, segm_thresh=0.5, return_debug=False, bucketed=False):
     """One image through the whole chain of `test.py:75-116`: preprocess -> net -> `get_boxes` on the maps
     where the network wrote them -> RoIRotate + recognition head + greedy CTC for every box ->
     (boxes (n, 9) numpy, texts); like the reference's loop, boxes whose text is empty are dropped
@@ -142,7 +152,8 @@ def infer_image(net, converter, im, detector=None, segm_thresh=0.5, return_debug
 
     The image is preprocessed into the dtype of the network's parameters (float32, bfloat16, float16), so
     `infer_image(net.to(torch.bfloat16), ...)` runs the whole chain in 16 bits with the same synchronisations; a tensor
-    passed instead of an image is used as it is.  The `detector` hook's maps may have any of the three dtypes."""
+    passed instead of an image is used as it is.  The `detector` hook's maps may have any of the three dtypes.
+    `bucketed`: see `batched` (opt-in; same boxes, texts and crops)."""
     from rroi_align.nms import get_boxes
     device, dtype = _net_device_dtype(net)
     im_data = preprocess(im, device, dtype) if not isinstance(im, torch.Tensor) else im
@@ -152,7 +163,8 @@ def infer_image(net, converter, im, detector=None, segm_thresh=0.5, return_debug
     else:
         s, r, a = score[0][0, 0], rbox[0][0], angle[0][0]
     boxes = get_boxes(s, r, a, segm_thresh)
-    out = batched(net, converter, feats, boxes, return_crops=return_debug, gw_host=target_widths_host(boxes))
+    out = batched(net, converter, feats, boxes, return_crops=return_debug, gw_host=target_widths_host(boxes),
+                  bucketed=bucketed)
     texts = out[0] if return_debug else out
     keep = [i for i, t in enumerate(texts) if len(t) > 0]
     res = (boxes[keep], [texts[i] for i in keep])
@@ -179,7 +191,7 @@ def _batch_front(net, ims, detector, segm_thresh):
     return im_data.shape[0], feats, decode_batch(s, r, a, segm_thresh)
 
 
-def _batch_back(net, converter, front, return_debug=False):
+def _batch_back(net, converter, front, return_debug=False, bucketed=False):
     """The second half, on the current stream: the boxes of every image (`merge_decoded`: two synchronisations, host merges),
     ONE RoIRotate launch for all their words, the head per pooled-width bucket, the strings."""
     from rroi_align.nms import merge_decoded
@@ -189,7 +201,7 @@ def _batch_back(net, converter, front, return_debug=False):
     boxes = np.concatenate(per_image, 0) if nimg else np.zeros((0, 9), np.float32)
     bidx = np.repeat(np.arange(nimg, dtype=np.float32), counts)
     out = batched(net, converter, feats, boxes, return_crops=return_debug, gw_host=target_widths_host(boxes) if len(boxes) else [],
-                  batch_index=bidx)
+                  batch_index=bidx, bucketed=bucketed)
     texts = out[0] if return_debug else out
     res, at = [], 0
     for b in range(nimg):
@@ -200,7 +212,7 @@ def _batch_back(net, converter, front, return_debug=False):
     return (res, (per_image, out, feats)) if return_debug else res
 
 
-def infer_batch(net, converter, ims, detector=None, segm_thresh=0.5, return_debug=False):
+def infer_batch(net, converter, ims, detector=None, segm_thresh=0.5, return_debug=False, bucketed=False):
     """SEVERAL images of one size through the chain of `test.py:75-116` at once (round 6; the reference's loop takes one
     image per pass, `test.py:62-75` -- its test set, ICDAR 2015, is 1280 x 720 throughout): ONE pass through the network
     for the batch, `get_boxes` per image (every image's device decode is enqueued before the first read-back: one wait
@@ -214,16 +226,17 @@ def infer_batch(net, converter, ims, detector=None, segm_thresh=0.5, return_debu
     rbox (N, 4, h, w), angle (N, 2, h, w))`."""
     if len(ims) == 0:
         return ([], ([], ([], [], []), None)) if return_debug else []
-    return _batch_back(net, converter, _batch_front(net, ims, detector, segm_thresh), return_debug)
+    return _batch_back(net, converter, _batch_front(net, ims, detector, segm_thresh), return_debug, bucketed)
 
 
-def infer_stream(net, converter, batches, detector=None, segm_thresh=0.5):
+def infer_stream(net, converter, batches, detector=None, segm_thresh=0.5, bucketed=False):
     """`infer_batch` over a SEQUENCE of batches with two batches in flight (a generator: one list of (boxes, texts) per
     batch, in order): the network pass of batch k + 1 is enqueued on the caller's stream BEFORE batch k's boxes are read
     back, and batch k's second half -- read-backs, host merges, RoIRotate, head, strings -- runs on a second stream
     beside it.  The device never waits for the host's merges and string building, the host never waits for a network
     pass it does not need yet; results are those of `infer_batch` (same kernels on the same data).  `detector`: a callable
-    `(k, im_data) -> maps` (the batch's index first), or None."""
+    `(k, im_data) -> maps` (the batch's index first), or None.  `bucketed`: see `batched`; everything the bucketed op
+    allocates (crops, tables, scratch) is allocated on the side stream that uses it, so the invariant below covers it."""
     device = next(net.parameters()).device
     side = torch.cuda.Stream(device=device)
 
@@ -240,7 +253,7 @@ def infer_stream(net, converter, batches, detector=None, segm_thresh=0.5):
             cnt.record_stream(side)
         with torch.cuda.stream(side):
             side.wait_event(ready)
-            res = _batch_back(net, converter, front)      # its read-backs synchronise `side` only
+            res = _batch_back(net, converter, front, bucketed=bucketed)      # its read-backs synchronise `side` only
         return res
     prev = None
     for k, ims in enumerate(batches):

@@ -54,6 +54,30 @@ class BatchedRRoiAlign(Module):
         return crops, gw
 
 
+class BucketedRRoiAlign(Module):
+    """forward(features, quads, batch_index=None, widths=None) -> (buckets, target_gw): the crops of BatchedRRoiAlign
+    without the dense tensor -- `buckets` = [(index (R_b,), crops (R_b, C, target_h, W_b))] in ascending width, crop j of a
+    bucket bit for bit BatchedRRoiAlign's crops[index[j], :, :, :W_b].  One launch chain whatever the number of widths;
+    the head consumes every bucket as it is.  Width rule and ROI rows are rois_from_quads'.  `widths`: the boxes' pooled
+    widths when the caller has them on the host already (fots_e2e.pipeline.target_widths_host); None reads target_gw
+    back once.  Crops are NCHW."""
+
+    def __init__(self, target_h=11, spatial_scale=1.0 / 4, trig=0, deterministic=None):
+        super(BucketedRRoiAlign, self).__init__()
+        self.target_h = int(target_h)
+        self.spatial_scale = float(spatial_scale)
+        self.trig = int(trig)
+        self.deterministic = deterministic
+
+    def forward(self, features, quads, batch_index=None, widths=None):
+        from .modules.rroi_align import _RRoiAlignBucketed
+        rois, gw = rois_from_quads(quads, batch_index, False, self.target_h)
+        if widths is None:
+            widths = gw.cpu().tolist()
+        buckets = _RRoiAlignBucketed(self.target_h, self.spatial_scale, self.trig, self.deterministic)(features, rois, widths)
+        return buckets, gw
+
+
 _warned_ambiguous_jitter = False
 
 

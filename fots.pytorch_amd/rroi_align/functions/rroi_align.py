@@ -95,3 +95,63 @@ class RRoiAlignFunction(object):
                                          float(self.spatial_scale), trig=self.trig,
                                          deterministic=_deterministic(self.deterministic))
         return grad_input, None
+
+
+class _RRoiAlignBucketedOp(Function):
+    """RoIRotate with one pooled width per ROI (rroi_align.forward_bucketed / backward_bucketed): the outputs are the
+    buckets' crop tensors, in the order of bucket_layout(widths).  Autocast, dtypes and the deterministic flag follow
+    _RRoiAlignOp; the backward takes every bucket's gradient where autograd left it (a bucket whose gradient is None
+    contributes nothing; a non-contiguous one is made contiguous on its own)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, features, rois, pooled_height, widths, spatial_scale, trig=rroi_align.TRIG_DOUBLE, deterministic=None):
+        ctx.pooled_height = pooled_height
+        ctx.widths = widths
+        ctx.spatial_scale = spatial_scale
+        ctx.feature_size = features.size()
+        ctx.channels_last_grad = (features.dim() == 4 and not features.is_contiguous()
+                                  and features.is_contiguous(memory_format=torch.channels_last))
+        ctx.trig = trig
+        ctx.deterministic = deterministic
+        ctx.dtype = features.dtype
+        ctx.save_for_backward(rois)
+        ctx.set_materialize_grads(False)   # an unused bucket's gradient stays None: nothing is read for it
+        buckets = rroi_align.forward_bucketed(features, rois, pooled_height, widths, spatial_scale, trig=trig)
+        return tuple(crops for _, crops in buckets)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        (rois,) = ctx.saved_tensors
+        grad_input = None
+        if ctx.needs_input_grad[0]:
+            grads = [None if g is None else g.to(ctx.dtype) for g in grads]
+            grad_input = rroi_align.backward_bucketed(grads, rois, ctx.feature_size, ctx.pooled_height, ctx.widths,
+                                                      ctx.spatial_scale, channels_last_grad=ctx.channels_last_grad,
+                                                      trig=ctx.trig, deterministic=_deterministic(ctx.deterministic))
+            grad_input = grad_input.to(ctx.dtype)   # (no bucket has a gradient: the zero fill is float32)
+        return grad_input, None, None, None, None, None, None
+
+
+class RRoiAlignBucketedFunction(object):
+    """``RRoiAlignBucketedFunction(ph, scale)(features, rois, widths) -> [(index, crops (R_b, C, ph, W_b))]`` in
+    ascending width; ``widths``: R host ints."""
+
+    def __init__(self, pooled_height, spatial_scale, trig=rroi_align.TRIG_DOUBLE, deterministic=None):
+        self.pooled_height = pooled_height
+        self.spatial_scale = spatial_scale
+        self.trig = int(trig)
+        self.deterministic = deterministic
+
+    def __call__(self, features, rois, widths):
+        widths = tuple(int(w) for w in widths)
+        layout = rroi_align.bucket_layout(widths)
+        if not layout:
+            return []
+        crops = _RRoiAlignBucketedOp.apply(features, rois, int(self.pooled_height), widths, float(self.spatial_scale),
+                                           self.trig, self.deterministic)
+        index = rroi_align._bucket_tables(widths, features.shape[1], int(self.pooled_height), crops[0].element_size(),
+                                          features.device).idx
+        return list(zip(index, crops))

@@ -43,3 +43,28 @@ class _RRoiAlign(Module):
     def extra_repr(self):
         return "pooled_height={}, pooled_width={}, spatial_scale={}".format(
             self.pooled_height, self.pooled_width, self.spatial_scale)
+
+
+class _RRoiAlignBucketed(Module):
+    """RoIRotate with one pooled width PER ROI: ``_RRoiAlignBucketed(pooled_height, spatial_scale)(features, rois, widths)``
+    -> ``[(index LongTensor (R_b,), crops (R_b, C, pooled_height, W_b))]`` in ascending width, the ROI order kept inside a
+    bucket; ``widths`` is a host sequence of R ints.  Crop j of a bucket is bit for bit what
+    ``_RRoiAlign(pooled_height, W_b, spatial_scale)(features, rois[index])[j]`` returns, but nothing wider is ever written
+    and no bucket is sliced or copied out of a dense tensor: one launch chain for all widths, forward and backward.
+    ``trig`` / ``deterministic`` and the dtype rules are ``_RRoiAlign``'s; features and crops are NCHW (channels_last
+    features are made contiguous; their gradient comes back channels_last)."""
+
+    def __init__(self, pooled_height, spatial_scale, trig=0, deterministic=None):
+        super(_RRoiAlignBucketed, self).__init__()
+        self.deterministic = None if deterministic is None else bool(deterministic)
+        self.trig = int(trig)
+        self.pooled_height = int(pooled_height)
+        self.spatial_scale = float(spatial_scale)
+
+    def forward(self, features, rois, widths):
+        from ..functions.rroi_align import RRoiAlignBucketedFunction
+        return RRoiAlignBucketedFunction(self.pooled_height, self.spatial_scale, self.trig, self.deterministic)(
+            features, rois, widths)
+
+    def extra_repr(self):
+        return "pooled_height={}, spatial_scale={}".format(self.pooled_height, self.spatial_scale)

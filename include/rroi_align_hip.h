@@ -316,6 +316,71 @@ int rroi_align_backward_plan_typed(int dtype, int top_diff_layout, int bottom_di
                                    int caller, rroi_align_plan* plan);
 
 /* ------------------------------------------------------------------------- *
+ * 2b. Bucketed RoIRotate: one pooled width PER ROI, one launch chain per call.
+ *     Arrived after 0.10.0 under the same version string: a caller detects it by symbol.
+ *
+ *     RoIRotate is a variable-width operator -- a word keeps its aspect ratio -- but the calls of section 2 take one
+ *     pooled_width, so a caller pools every ROI at the widest width of the batch and cuts its width buckets out afterwards.
+ *     Here crop i is its own dense NCHW block (C, PH, W_i), found through a DEVICE table with one 16-byte row per ROI:
+ *     its address and its pooled width.  Addresses are independent: the crops of one width usually form one contiguous
+ *     (R_b, C, PH, W_b) tensor per bucket, each bucket an allocation of its own (autograd hands the backward one gradient
+ *     tensor per bucket: they are consumed in place).  The value of element (c, ph, pw) of a crop depends on the ROI and
+ *     on (ph, pw), never on the pooled width (kernel.cu:49-107), so crop i is, bit for bit, the first W_i columns of the
+ *     same ROI pooled by the calls of section 2 at any width >= W_i.
+ *
+ *     Forward: EVERY element of every crop is written (masked bins are zeros; the crops need not be initialised) and
+ *     NOTHING outside a crop's C * PH * W_i elements is.  Backward: the feature gradient (B, C, H, W), NCHW or NHWC, is
+ *     fully overwritten; columns >= W_i do not exist.  Features and crops are NCHW, of element type `dtype` (RROI_DTYPE_*);
+ *     rois are fp32.
+ *     A row the host cannot check -- pooled_width < 1 or > max_pooled_width, or a NULL address -- is SKIPPED: nothing of
+ *     that crop is read or written and it contributes nothing to the gradient; its neighbours are unaffected.
+ *     Alignment: any crop address aligned to the element size gives correct results.  The caller STATES two facts about
+ *     its table: `width_multiple`, a common divisor of all widths (1 says nothing), and `crop_alignment`, a power of two
+ *     that divides every address in bytes (the element size says nothing).  The forward's fast form for many ROIs -- the
+ *     prologue of the two-launch path followed by a ragged gather with 16-byte stores -- needs
+ *     pooled_height * width_multiple % 16 == 0 and crop_alignment % 64 == 0; in that form a row that breaks the stated
+ *     facts is skipped like a row with a bad width.  `sum_pooled_widths` (the sum over the table) is the call's real
+ *     output size, by which RROI_PATH_AUTO chooses.
+ *     Forward paths: RROI_PATH_AUTO; RROI_PATH_DIRECT = the ragged patch kernel (one launch, any widths, addresses and
+ *     R); RROI_PATH_TILED = the ragged gather (refused where its contract does not hold); | RROI_PATH_TRIG_FP32.  AUTO
+ *     takes the patch kernel for small outputs and wherever the gather's contract does not hold.  RROI_PATH_FUSED: 0.
+ *     Backward paths: RROI_PATH_AUTO, RROI_PATH_TILED_LISTS, RROI_PATH_TILED_BUCKETS; | RROI_PATH_TRIG_FP32;
+ *     RROI_PATH_AUTO | RROI_PATH_DETERMINISTIC = the ORDERED plan with the contract stated there (bit for bit the dense
+ *     ORDERED gradient of the crops zero-padded to max_pooled_width).  Every other path returns 0; a ragged call is
+ *     refused where the list gathers' 32-bit indices do not hold (the rule of 16-bit calls, above).
+ *     Returns 1 / 0 / -hipError; every non-pointer argument is checked before any launch; a NULL pointer with
+ *     num_rois > 0 returns 0; num_rois == 0 returns 1 (the backward zero-fills bottom_diff).  The calls only enqueue on
+ *     `stream` and can be captured into a HIP graph.  Workspace: the sizes below (those of the dense calls at
+ *     max_pooled_width); the patch kernel needs none (NULL / 0 accepted).
+ * ------------------------------------------------------------------------- */
+typedef struct rroi_align_crop {
+    void* data;       /* (C, PH, pooled_width) elements, contiguous */
+    int pooled_width; /* 1 .. max_pooled_width */
+    int reserved;     /* 0 */
+} rroi_align_crop;    /* 16 bytes */
+#define RROI_PLAN_KERNEL_STRIDED_RAGGED 5 /* plan.kernel of the bucketed two-launch forward */
+size_t rroi_align_forward_bucketed_workspace_bytes(int batch_size, int channels, int height, int width, int num_rois);
+size_t rroi_align_backward_bucketed_workspace_bytes(int batch_size, int channels, int height, int width, int num_rois,
+                                                    int pooled_height, int max_pooled_width);
+int rroi_align_forward_bucketed_hip(const void* features, int dtype, float spatial_scale, int batch_size, int num_rois,
+                                    int height, int width, int channels, int pooled_height, int max_pooled_width,
+                                    long long sum_pooled_widths, int width_multiple, int crop_alignment, const float* rois,
+                                    const rroi_align_crop* crops, void* workspace, size_t workspace_bytes, int path,
+                                    void* stream);
+int rroi_align_backward_bucketed_hip(const rroi_align_crop* top_diffs, int dtype, int bottom_diff_layout, float spatial_scale,
+                                     int batch_size, int num_rois, int height, int width, int channels, int pooled_height,
+                                     int max_pooled_width, const float* rois, void* bottom_diff, void* workspace,
+                                     size_t workspace_bytes, int path, void* stream);
+/* Plan queries, host only as in section 2.  Forward: family RROI_PLAN_FWD_DIRECT_K2P (the ragged patch kernel) or
+ * RROI_PLAN_FWD_TWO_LAUNCH with kernel RROI_PLAN_KERNEL_STRIDED_RAGGED, groups 1, ntiles = the widest crop's tiles (the
+ * item space; a ROI has ceil(PH * W_i / 64) of them).  Backward: RROI_PLAN_BWD_LISTS / _BUCKETS / _ORDERED only. */
+int rroi_align_forward_bucketed_plan(int dtype, int batch_size, int num_rois, int height, int width, int channels,
+                                     int pooled_height, int max_pooled_width, long long sum_pooled_widths, int width_multiple,
+                                     int crop_alignment, int path, rroi_align_plan* plan);
+int rroi_align_backward_bucketed_plan(int dtype, int bottom_diff_layout, int batch_size, int num_rois, int height, int width,
+                                      int channels, int pooled_height, int max_pooled_width, int path, rroi_align_plan* plan);
+
+/* ------------------------------------------------------------------------- *
  * 3. The callers' ROI construction, on the device.
  *    quads (n, 8) fp32 [x0,y0,x1,y1,x2,y2,x3,y3] -> rois (n, 6) fp32 rows for the
  *    op, plus (optionally) each box's pooled width by the inference rule.
@@ -427,7 +492,7 @@ int rroi_align_get_trig_recipe_hip(void);
 
 /* Identification: "rroi_align_hip <version> gfx950" (0.7.0: per-call trig recipe, device-wide setter removed; 0.8.0: launcher scratch reused within a capture, table of 64, stats; 0.9.0: plan query; 0.10.0: bfloat16 / float16 tensors).
  * The typed callers' entry points (rroi_rbox_decode_typed_hip, rroi_ctc_greedy_decode_typed_hip) arrived after 0.10.0 under
- * the same version string: a caller detects them by symbol. */
+ * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b. */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
