@@ -266,6 +266,11 @@ PatchMap make_patch_map(int pooled_height, int pooled_width)
     return pm;
 }
 
+// A caller's workspace: not NULL and a multiple of 256 bytes -- every sub-array of carve / carve_bwd sits at an
+// align_up(..., 256) offset from it and is indexed as 16-byte vectors and 128-byte lines.  Beyond that the base address is
+// free (carve_bwd's two roundings to 4 KiB of the address are in its size).
+inline bool workspace_ok(const void* ws) { return ws && (reinterpret_cast<uintptr_t>(ws) & 255u) == 0; }
+
 struct Workspace {
     Affine* aff;
     int* sort_rank;    // XCD groups: the counting sort's scratch and ...
@@ -1253,7 +1258,7 @@ static int launch_forward(const FwdDispatch& P, const T* features, int feature_l
     }
 
     const Workspace ws = carve(workspace, batch_size, channels, height, width, num_rois, feature_layout);
-    if (!workspace || workspace_bytes < ws.bytes) return 0;
+    if (!workspace_ok(workspace) || workspace_bytes < ws.bytes) return 0;
     const int HW = height * width;
     const bool zero_copy = P.zero_copy;
     const float* map = ws.cm;
@@ -1430,7 +1435,7 @@ static int launch_backward(const BwdDispatch& P, const T* top_diff, float spatia
     }
 
     const BwdWorkspace ws = carve_bwd(workspace, batch_size, channels, height, width, num_rois, NB);
-    if (!workspace || workspace_bytes < ws.bytes) return 0;
+    if (!workspace_ok(workspace) || workspace_bytes < ws.bytes) return 0;
     if (!kF32 && (P.family == RROI_PLAN_BWD_ATOMIC || td_nhwc || accumulate)) return 0;
     if (ragged && (td_nhwc || accumulate || !(P.family == RROI_PLAN_BWD_LISTS || P.family == RROI_PLAN_BWD_BUCKETS ||
                                                P.family == RROI_PLAN_BWD_ORDERED)))
@@ -2069,7 +2074,7 @@ int launch_forward_bucketed(const FwdDispatch& P, const T* features, float spati
     }
     if (P.family != RROI_PLAN_FWD_TWO_LAUNCH) return 0;
     const Workspace ws = carve(workspace, batch_size, channels, height, width, num_rois, RROI_LAYOUT_NCHW);
-    if (!workspace || workspace_bytes < ws.bytes) return 0;
+    if (!workspace_ok(workspace) || workspace_bytes < ws.bytes) return 0;
     const int nchunks = P.nchunks;
     const int st = launch_forward_prologue(features, ws, false, 1, false, (T*)nullptr, batch_size, num_rois, height, width,
                                            channels, pooled_height, max_pooled_width, rois, spatial_scale, P.trig, nchunks, stream);

@@ -153,7 +153,14 @@ int rroi_align_launcher_trig_recipe(void);
 #define RROI_PATH_DETERMINISTIC 0x200
 
 /* Bytes of scratch the tiled path needs for this problem (0 for the direct
- * path).  The caller owns the scratch; its contents are dead after the call. */
+ * path).  The caller owns the scratch; its contents are dead after the call.
+ * The workspace pointer must be a multiple of 256 bytes -- every sub-array the library carves out of it sits at an
+ * offset rounded up to 256 -- and a plan that uses the workspace returns 0, before any launch, for one that is not
+ * (as for NULL or fewer bytes than these queries report).  Beyond that the base address is free: the backward's size
+ * already includes the two roundings to 4 KiB of the address it makes, whatever the base is.  A call writes nothing
+ * outside [workspace, workspace + the queried bytes), whatever larger size it is told, and reads nothing of what the
+ * workspace held before the call: it need not be cleared, and may hold anything.  The plans that take no workspace
+ * (RROI_PATH_DIRECT, RROI_PATH_FUSED) accept any pointer and size, NULL / 0 included, and touch none of it. */
 size_t rroi_align_forward_workspace_bytes(int batch_size, int channels, int height, int width,
                                           int num_rois, int feature_layout);
 size_t rroi_align_backward_workspace_bytes(int batch_size, int channels, int height, int width,
@@ -351,7 +358,9 @@ int rroi_align_backward_plan_typed(int dtype, int top_diff_layout, int bottom_di
  *     Returns 1 / 0 / -hipError; every non-pointer argument is checked before any launch; a NULL pointer with
  *     num_rois > 0 returns 0; num_rois == 0 returns 1 (the backward zero-fills bottom_diff).  The calls only enqueue on
  *     `stream` and can be captured into a HIP graph.  Workspace: the sizes below (those of the dense calls at
- *     max_pooled_width); the patch kernel needs none (NULL / 0 accepted).
+ *     max_pooled_width); the patch kernel needs none (NULL / 0 accepted).  As in section 2 the workspace pointer must be
+ *     a multiple of 256 bytes (0 otherwise, before any launch, from a plan that uses it); beyond that the base address
+ *     is free, nothing outside the queried bytes is written and nothing the workspace held before is read.
  * ------------------------------------------------------------------------- */
 typedef struct rroi_align_crop {
     void* data;       /* (C, PH, pooled_width) elements, contiguous */

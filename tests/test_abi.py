@@ -191,3 +191,75 @@ def test_write_probe_and_trig_recipe_hooks():
     geom = torch.empty(1, 4, 16, 2, device="cuda")
     assert ext._lib.rroi_align_bin_centres_trig_hip(0.25, 1, 16, 16, 4, 16, R.data_ptr(), geom.data_ptr(), 5, st) == 0
     assert ext._lib.rroi_nms_record_format() == 2
+
+
+def test_misaligned_workspace_is_refused_before_any_launch():
+    """The carve places every sub-array at an align_up(..., 256) offset from the workspace pointer, so the pointer must be
+    a multiple of 256 bytes (the header, sections 2 and 2b): every entry point that takes a workspace returns 0 for a plan
+    that uses it -- next to the size check, before any launch.  Host code only: the addresses are fabricated, so the test
+    does not run where a launch could follow (with a GPU); without one, a call that gets past the check comes back with
+    a negative HIP status, not 0.  Plans that take no workspace accept any pointer."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a fabricated address must never reach a launch: the check is pure host code, tested without a GPU")
+    from rroi_align._ext import rroi_align as ext
+    L = ext._lib
+    P = 0x7f0000000000                    # non-null, never dereferenced on the host
+    B, C, H, W, R, ph, pw = 2, 36, 13, 18, 40, 8, 16
+    nf = L.rroi_align_forward_workspace_bytes(B, C, H, W, R, 0)
+    nb = L.rroi_align_backward_workspace_bytes(B, C, H, W, R, ph, pw)
+    big = 1 << 30                         # the stated size is never the reason
+    DET = ext.PATH_DETERMINISTIC
+
+    def calls(ws, fpath, bpath):
+        return {
+            "forward_hip": L.rroi_align_forward_hip(P, 0, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big, fpath, None),
+            "forward_layout_hip": L.rroi_align_forward_layout_hip(P, 0, 1, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big, fpath, None),
+            "forward_typed_hip": L.rroi_align_forward_typed_hip(P, 1, 0, 0, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big, fpath, None),
+            "forward_stages_hip": L.rroi_align_forward_stages_hip(P, 0, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big, fpath,
+                                                                  ext.STAGE_PROLOGUE, None),
+            "backward_hip": L.rroi_align_backward_hip(P, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big, bpath, None),
+            "backward_layout_hip": L.rroi_align_backward_layout_hip(P, 0, 1, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big,
+                                                                    ext.PATH_TILED_LISTS, None),
+            "backward_typed_hip": L.rroi_align_backward_typed_hip(P, 2, 0, 0, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big,
+                                                                  ext.PATH_TILED_BUCKETS, None),
+        }
+
+    def bucketed(ws, fpath, bpath):
+        return {
+            "forward_bucketed_hip": L.rroi_align_forward_bucketed_hip(P, 0, 0.25, B, R, H, W, C, ph, pw, R * pw, 16, 256, P, P,
+                                                                      ws, big, fpath, None),
+            "backward_bucketed_hip": L.rroi_align_backward_bucketed_hip(P, 0, 0, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big,
+                                                                        bpath, None),
+        }
+    assert nf > 0 and nb > 0
+    for residue in (4, 16, 128):
+        ws = P + residue
+        got = calls(ws, ext.PATH_TILED, ext.PATH_TILED_INKERNEL)
+        got.update(bucketed(ws, ext.PATH_TILED, ext.PATH_TILED_LISTS))
+        got["backward_hip ordered"] = L.rroi_align_backward_hip(P, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big, DET, None)
+        got["backward_hip atomic"] = L.rroi_align_backward_hip(P, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big,
+                                                               ext.PATH_TILED_ATOMIC, None)
+        got["backward_bucketed_hip ordered"] = L.rroi_align_backward_bucketed_hip(P, 0, 0, 0.25, B, R, H, W, C, ph, pw, P, P,
+                                                                                  ws, big, DET, None)
+        assert all(v == 0 for v in got.values()), (residue, got)
+        # the plans that take no workspace keep accepting anything: they get as far as the launch
+        free = {
+            "forward_hip direct": L.rroi_align_forward_hip(P, 0, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big, ext.PATH_DIRECT, None),
+            "forward_hip fused": L.rroi_align_forward_hip(P, 0, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big, ext.PATH_FUSED, None),
+            "forward_typed_hip direct": L.rroi_align_forward_typed_hip(P, 1, 0, 0, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big,
+                                                                       ext.PATH_DIRECT, None),
+            "forward_stages_hip direct": L.rroi_align_forward_stages_hip(P, 0, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big,
+                                                                         ext.PATH_DIRECT, ext.STAGE_GATHER, None),
+            "backward_hip direct": L.rroi_align_backward_hip(P, 0.25, B, R, H, W, C, ph, pw, P, P, ws, big, ext.PATH_DIRECT, None),
+            "forward_bucketed_hip patch": bucketed(ws, ext.PATH_DIRECT, ext.PATH_TILED_LISTS)["forward_bucketed_hip"],
+        }
+        assert all(v != 0 for v in free.values()), (residue, free)
+    # an aligned pointer passes the check whatever its offset within a page (the backward's size holds the roundings)
+    for offset in (0, 256, 2304, 3840):
+        got = calls(P + offset, ext.PATH_TILED, ext.PATH_TILED_INKERNEL)
+        got.update(bucketed(P + offset, ext.PATH_TILED, ext.PATH_TILED_LISTS))
+        assert all(v != 0 for v in got.values()), (offset, got)
+    # ... and the size check next to it still holds: one byte short is refused
+    assert L.rroi_align_forward_hip(P, 0, 0.25, B, R, H, W, C, ph, pw, P, P, P, nf - 1, ext.PATH_TILED, None) == 0
+    assert L.rroi_align_backward_hip(P, 0.25, B, R, H, W, C, ph, pw, P, P, P, nb - 1, ext.PATH_TILED_LISTS, None) == 0
