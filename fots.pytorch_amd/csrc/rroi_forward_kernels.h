@@ -457,7 +457,7 @@ __global__ void rroi_affine_kernel(const float* __restrict__ rois, int num_rois,
 // row's partial sectors together), 16-byte stores at dword alignment.  dbg: bit 0 drops the stores, bit 1
 // the tap loads (ablations), bit 5 the reference-ABI launcher's mode.  (The per-workgroup time stamps, the
 // contiguous-items knob and the free-first-item ablation of round 4 are tools/experiments/r04_wg_trace_instrumentation.patch.)
-// Shipped instantiations: the switch in forward_impl (rroi_align_hip.hip).
+// Shipped instantiations: the switch in launch_forward (rroi_host_launch.h).
 // ------------------------------------------------------------------------------------
 constexpr int kStoreAux = 2;      // output stores stream (nt) ...
 constexpr int kMinorStores = 1;   // ... except this many of a tile's eight, which go out write-through (kMinorAux)

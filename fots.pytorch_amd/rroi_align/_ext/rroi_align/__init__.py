@@ -186,12 +186,9 @@ def forward_plan(batch_size, channels, height, width, num_rois, pooled_height, p
                  trig=0, dtype=DTYPE_FP32) -> Plan:
     """The plan a forward call with these arguments runs (host only, no GPU needed); ValueError where the call
     would refuse them.  dtype: of the features and crops (a torch dtype or DTYPE_*; the default is the fp32 query)."""
-    code = dtype_code(dtype)
-    args = (feature_layout, top_layout, batch_size, num_rois, height, width, channels, pooled_height, pooled_width,
-            _path_word(path, trig), caller)
-    if code == DTYPE_FP32:
-        return _plan(_lib.rroi_align_forward_plan, args, "rroi_align_forward_plan")
-    return _plan(_lib.rroi_align_forward_plan_typed, (code,) + args, "rroi_align_forward_plan_typed")
+    args = (dtype_code(dtype), feature_layout, top_layout, batch_size, num_rois, height, width, channels, pooled_height,
+            pooled_width, _path_word(path, trig), caller)
+    return _plan(_lib.rroi_align_forward_plan_typed, args, "rroi_align_forward_plan_typed")
 
 
 def backward_plan(batch_size, channels, height, width, num_rois, pooled_height, pooled_width,
@@ -200,12 +197,9 @@ def backward_plan(batch_size, channels, height, width, num_rois, pooled_height, 
     """The plan a backward call with these arguments runs (host only, no GPU needed); ValueError where the call
     would refuse them.  dtype: of grad_output and the gradient (a torch dtype or DTYPE_*; the default is the fp32
     query).  deterministic: the query of a call with PATH_DETERMINISTIC (backward(deterministic=True))."""
-    code = dtype_code(dtype)
-    args = (top_diff_layout, bottom_diff_layout, batch_size, num_rois, height, width, channels, pooled_height,
-            pooled_width, _path_word(path, trig, deterministic), caller)
-    if code == DTYPE_FP32:
-        return _plan(_lib.rroi_align_backward_plan, args, "rroi_align_backward_plan")
-    return _plan(_lib.rroi_align_backward_plan_typed, (code,) + args, "rroi_align_backward_plan_typed")
+    args = (dtype_code(dtype), top_diff_layout, bottom_diff_layout, batch_size, num_rois, height, width, channels,
+            pooled_height, pooled_width, _path_word(path, trig, deterministic), caller)
+    return _plan(_lib.rroi_align_backward_plan_typed, args, "rroi_align_backward_plan_typed")
 
 
 def version() -> str:
@@ -304,6 +298,19 @@ def _require_cuda_f32(t: torch.Tensor, name: str, dtypes=(torch.float32,)) -> No
 _IO_DTYPES = (torch.float32, torch.bfloat16, torch.float16)   # features / crops, grad_output / gradient
 
 
+def _require_features_rois(features: torch.Tensor, rois: torch.Tensor) -> int:
+    """What forward() and forward_bucketed() ask of their tensors; returns the DTYPE_* of the features."""
+    _require_cuda_f32(features, "features", _IO_DTYPES)
+    _require_cuda_f32(rois, "rois")
+    if features.dim() != 4:
+        raise ValueError(f"features must be (B,C,H,W), got {tuple(features.shape)}")
+    if rois.dim() != 2 or rois.size(1) != 6:
+        raise ValueError(f"rois must be (R,6) [batch,cx,cy,h,w,angle_deg], got {tuple(rois.shape)}")
+    if rois.device != features.device:
+        raise ValueError("features and rois must be on the same device")
+    return _DTYPES[features.dtype]
+
+
 # --------------------------------------------------------------------------- native path
 def forward(features: torch.Tensor, rois: torch.Tensor, pooled_height: int, pooled_width: int,
             spatial_scale: float, path: int = PATH_AUTO, channels_last_out: bool = False,
@@ -316,15 +323,7 @@ def forward(features: torch.Tensor, rois: torch.Tensor, pooled_height: int, pool
     each crop element once: bit for bit the fp32 call on the widened map, rounded; channels_last 16-bit features are
     made contiguous first, PATH_FUSED is fp32 only).  rois: float32."""
     word = _path_word(path, trig)
-    _require_cuda_f32(features, "features", _IO_DTYPES)
-    _require_cuda_f32(rois, "rois")
-    code = _DTYPES[features.dtype]
-    if features.dim() != 4:
-        raise ValueError(f"features must be (B,C,H,W), got {tuple(features.shape)}")
-    if rois.dim() != 2 or rois.size(1) != 6:
-        raise ValueError(f"rois must be (R,6) [batch,cx,cy,h,w,angle_deg], got {tuple(rois.shape)}")
-    if rois.device != features.device:
-        raise ValueError("features and rois must be on the same device")
+    code = _require_features_rois(features, rois)
     B, C, H, W = features.shape
     R = rois.size(0)
     ph, pw = int(pooled_height), int(pooled_width)
@@ -348,15 +347,10 @@ def forward(features: torch.Tensor, rois: torch.Tensor, pooled_height: int, pool
         nbytes = 0 if path in (PATH_DIRECT, PATH_FUSED) else _lib.rroi_align_forward_workspace_bytes(B, C, H, W, R, layout)
         ws = _workspace(features.device, nbytes)
         top_layout = LAYOUT_NHWC if channels_last_out else LAYOUT_NCHW
-        if code == DTYPE_FP32:
-            st = _lib.rroi_align_forward_layout_hip(features.data_ptr(), layout, top_layout,
-                                                    float(spatial_scale), B, R, H, W, C, ph, pw, rois.data_ptr(),
-                                                    out.data_ptr(), ws.data_ptr(), nbytes, word, _stream())
-        else:
-            st = _lib.rroi_align_forward_typed_hip(features.data_ptr(), code, layout, top_layout, float(spatial_scale),
-                                                   B, R, H, W, C, ph, pw, rois.data_ptr(), out.data_ptr(),
-                                                   ws.data_ptr(), nbytes, word, _stream())
-    _check(st, "rroi_align_forward_hip" if code == DTYPE_FP32 else "rroi_align_forward_typed_hip")
+        st = _lib.rroi_align_forward_typed_hip(features.data_ptr(), code, layout, top_layout, float(spatial_scale),
+                                               B, R, H, W, C, ph, pw, rois.data_ptr(), out.data_ptr(),
+                                               ws.data_ptr(), nbytes, word, _stream())
+    _check(st, "rroi_align_forward_typed_hip")
     return out
 
 
@@ -398,15 +392,10 @@ def backward(grad_output: torch.Tensor, rois: torch.Tensor, feature_size, spatia
         nbytes = 0 if path == PATH_DIRECT else _lib.rroi_align_backward_workspace_bytes(B, C, H, W, R, ph, pw)
         ws = _workspace(grad_output.device, nbytes)
         bottom_layout = LAYOUT_NHWC if cl_grad else LAYOUT_NCHW
-        if code == DTYPE_FP32:
-            st = _lib.rroi_align_backward_layout_hip(grad_output.data_ptr(), layout, bottom_layout, float(spatial_scale),
-                                                     B, R, H, W, C, ph, pw, rois.data_ptr(), grad_in.data_ptr(),
-                                                     ws.data_ptr(), nbytes, word, _stream())
-        else:
-            st = _lib.rroi_align_backward_typed_hip(grad_output.data_ptr(), code, layout, bottom_layout,
-                                                    float(spatial_scale), B, R, H, W, C, ph, pw, rois.data_ptr(),
-                                                    grad_in.data_ptr(), ws.data_ptr(), nbytes, word, _stream())
-    _check(st, "rroi_align_backward_hip" if code == DTYPE_FP32 else "rroi_align_backward_typed_hip")
+        st = _lib.rroi_align_backward_typed_hip(grad_output.data_ptr(), code, layout, bottom_layout,
+                                                float(spatial_scale), B, R, H, W, C, ph, pw, rois.data_ptr(),
+                                                grad_in.data_ptr(), ws.data_ptr(), nbytes, word, _stream())
+    _check(st, "rroi_align_backward_typed_hip")
     return grad_in
 
 
@@ -524,12 +513,9 @@ def forward_bucketed_plan(batch_size, channels, height, width, pooled_height, wi
                           dtype=DTYPE_FP32, crop_alignment=256) -> Plan:
     """The plan a bucketed forward of these pooled widths runs (host only); ValueError where the call would refuse."""
     R, mx, sm, g = _bucketed_stats(widths)
-    p = _Plan()
-    st = _lib.rroi_align_forward_bucketed_plan(dtype_code(dtype), batch_size, R, height, width, channels, pooled_height, mx,
-                                               sm, g, int(crop_alignment), _path_word(path, trig), ctypes.byref(p))
-    if st != 1:
-        raise ValueError("rroi_align_forward_bucketed_plan: the call would refuse these arguments")
-    return Plan(*(getattr(p, n) for n in Plan._fields))
+    return _plan(_lib.rroi_align_forward_bucketed_plan,
+                 (dtype_code(dtype), batch_size, R, height, width, channels, pooled_height, mx, sm, g, crop_alignment,
+                  _path_word(path, trig)), "rroi_align_forward_bucketed_plan")
 
 
 def backward_bucketed_plan(batch_size, channels, height, width, pooled_height, widths, path=PATH_AUTO, trig=0,
@@ -549,15 +535,7 @@ def forward_bucketed(features: torch.Tensor, rois: torch.Tensor, pooled_height: 
     copied afterwards.  The buckets are views of ONE allocation (each starts on a 256-byte boundary).
     features: float32, bfloat16 or float16, made NCHW-contiguous; rois float32; path: PATH_AUTO / PATH_DIRECT / PATH_TILED."""
     word = _path_word(path, trig)
-    _require_cuda_f32(features, "features", _IO_DTYPES)
-    _require_cuda_f32(rois, "rois")
-    code = _DTYPES[features.dtype]
-    if features.dim() != 4:
-        raise ValueError(f"features must be (B,C,H,W), got {tuple(features.shape)}")
-    if rois.dim() != 2 or rois.size(1) != 6:
-        raise ValueError(f"rois must be (R,6) [batch,cx,cy,h,w,angle_deg], got {tuple(rois.shape)}")
-    if rois.device != features.device:
-        raise ValueError("features and rois must be on the same device")
+    code = _require_features_rois(features, rois)
     B, C, H, W = features.shape
     R, ph = rois.size(0), int(pooled_height)
     if len(widths) != R:
@@ -680,13 +658,11 @@ def ctc_greedy_decode(logits: torch.Tensor, lengths=None, return_labels: bool = 
         decoded = torch.empty((N, T), dtype=torch.int32, device=dev)
         dlen = torch.empty((N,), dtype=torch.int32, device=dev)
         labels = torch.empty((N, T), dtype=torch.int32, device=dev) if return_labels else None
-        tail = (N, K, T, lengths.data_ptr() if lengths is not None else None,
-                labels.data_ptr() if labels is not None else None, decoded.data_ptr(), dlen.data_ptr(), _stream())
-        if code == DTYPE_FP32:
-            st = _lib.rroi_ctc_greedy_decode_hip(logits.data_ptr(), *tail)
-        else:
-            st = _lib.rroi_ctc_greedy_decode_typed_hip(code, logits.data_ptr(), *tail)
-    _check(st, "rroi_ctc_greedy_decode_hip" if code == DTYPE_FP32 else "rroi_ctc_greedy_decode_typed_hip")
+        st = _lib.rroi_ctc_greedy_decode_typed_hip(code, logits.data_ptr(), N, K, T,
+                                                   lengths.data_ptr() if lengths is not None else None,
+                                                   labels.data_ptr() if labels is not None else None,
+                                                   decoded.data_ptr(), dlen.data_ptr(), _stream())
+    _check(st, "rroi_ctc_greedy_decode_typed_hip")
     return (decoded, dlen, labels) if return_labels else (decoded, dlen)
 
 

@@ -2,7 +2,7 @@
 every case run against the oracle).  A case names a problem -- shape, ROI generator, layouts, path, caller -- and the
 library's plan query (rroi_align_forward_plan / rroi_align_backward_plan) says which kernels it runs.  REQUIRED is the
 set of plan keys a shipped kernel runs under, read off the dispatch (plan_forward / plan_backward in
-fots.pytorch_amd/csrc/rroi_align_hip.hip); the table must cover it, every key that a sweep of shapes, layouts, paths and
+fots.pytorch_amd/csrc/rroi_host_plan.h); the table must cover it, every key that a sweep of shapes, layouts, paths and
 callers reaches (sweep()) must be REQUIRED or NOT_RUN with a reason, and every value of every plan enum must appear in
 REQUIRED or in UNREACHABLE -- so a new kernel, a new combination, or a moved threshold that leaves one unreached,
 fails by name."""

@@ -110,5 +110,21 @@ def test_the_carve_recomputation_is_the_librarys_and_the_offsets_move_both_round
     assert len(seconds) >= 3 and max(seconds) > 0, seconds
 
 
+def test_the_forward_carve_recomputation_is_the_librarys(ext):
+    """forward_used_bytes restates carve on the host: it is the size query for every forward row and every bucketed
+    forward row, and for a shape whose five extents all differ -- so that one of them taken for another shows."""
+    for r in WC.FORWARD:
+        c = r.case
+        assert WC.forward_used_bytes(c.B, c.C, c.H, c.W, c.R, c.fl) == WC.workspace_bytes(ext, r), c.name
+    for b in WC.BUCKETED + [WC.NO_WORKSPACE_BUCKETED]:
+        if b.kind == "fwd":
+            assert WC.forward_used_bytes(b.B, b.C, b.H, b.W, b.R, PC.NCHW) == WC.bucketed_workspace_bytes(ext, b), b.name
+    B, C, H, W, R = 3, 40, 17, 29, 5
+    assert WC.forward_used_bytes(B, C, H, W, R, PC.NCHW) == 380160
+    assert int(ext._lib.rroi_align_forward_workspace_bytes(B, C, H, W, R, PC.NCHW)) == 380160
+    assert int(ext._lib.rroi_align_forward_bucketed_workspace_bytes(B, C, H, W, R)) == 380160
+    assert int(ext._lib.rroi_align_forward_workspace_bytes(B, C, H, W, R, PC.NHWC)) == WC.forward_used_bytes(B, C, H, W, R, PC.NHWC)
+
+
 def test_not_run_names_its_reasons():
     assert len(WC.NOT_RUN) == 2 and all(len(v) > 40 for v in WC.NOT_RUN.values())

@@ -3,7 +3,7 @@ tests/test_gpu_workspace.py (GPU: every row run through the raw ABI inside a gua
 at several base addresses).  Plain data.
 
 Every tiled plan runs inside a scratch buffer the caller owns.  The rows name one problem per kernel form that indexes
-that buffer -- every carve of carve / carve_bwd (fots.pytorch_amd/csrc/rroi_align_hip.hip) with every consumer of it --
+that buffer -- every carve of carve / carve_bwd (fots.pytorch_amd/csrc/rroi_host_plan.h) with every consumer of it --
 on maps that are deliberately tiny and awkward:
     13 x 18   HW % 4 != 0, row pitch 19 (one pad pixel per row), key space padded to 16 x 24
     13 x 19   odd HW
@@ -238,8 +238,18 @@ def bucketed_workspace_bytes(ext, b):
     return int(ext._lib.rroi_align_backward_bucketed_workspace_bytes(b.B, b.C, b.H, b.W, b.R, b.ph, max(b.choices)))
 
 
+def forward_used_bytes(B, C, H, W, R, layout):
+    """Host-side recomputation of carve (rroi_host_plan.h), the forward's workspace: the affine table, the sort's rank
+    and order, and -- unless channels-last features are consumed in place -- the chunk-major copy with its spare pixel
+    per (image, chunk) slice.  No slack: the total is the size query's (tests/test_workspace_plan.py)."""
+    def up(n, a=256):
+        return -(-n // a) * a
+    copy = 0 if layout == NHWC else up(B * -(-C // 32) * (H * (W | 1) + 1) * 128)
+    return up(max(R, 1) * 32) + 2 * up(max(R, 1) * 4) + copy
+
+
 def backward_used_bytes(ext, B, C, H, W, R, ph, pw, offset):
-    """Host-side recomputation of carve_bwd (rroi_align_hip.hip) for a workspace that starts `offset` bytes after a 4 KiB
+    """Host-side recomputation of carve_bwd (rroi_host_plan.h) for a workspace that starts `offset` bytes after a 4 KiB
     boundary: (bytes from the base to the end of the last sub-array, the two roundings).  The size query adds a flat
     8192 for the two roundings to 4 KiB of the address, so 8192 - r1 - r2 bytes at the end of the workspace belong to
     no sub-array: an overrun of the last one lands there, not in a guard, unless that tail is checked too.  The
