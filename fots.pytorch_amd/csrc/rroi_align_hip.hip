@@ -25,7 +25,8 @@
 // Files: this one holds the C-ABI (each entry point: argument checks, plan, NULL checks, launch); everything else is
 // in parts that are included below, inside the anonymous namespace.  Device code: rroi_device_common.h (constants,
 // geometry recipe, descriptor helpers), rroi_forward_kernels.h, rroi_backward_kernels.h, rroi_backward_tile_kernels.h,
-// rroi_callers_kernels.h, rroi_nms_kernels.h (+ rroi_nms_host.h, host C++).  Host side: rroi_host_plan.h (tuning table,
+// rroi_callers_kernels.h, rroi_nms_kernels.h (+ rroi_nms_host.h, host C++), rroi_depthwise_kernels.h (+ rroi_depthwise_host.h:
+// the network's depthwise 3x3 convolution).  Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch), rroi_host_scratch.h (the launchers' scratch), rroi_host_launch.h
 // (the launches).
 #include <hip/hip_runtime.h>
@@ -54,10 +55,12 @@ namespace {
 #include "rroi_callers_kernels.h"
 #include "rroi_nms_kernels.h"
 #include "rroi_nms_host.h"
+#include "rroi_depthwise_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
 #include "rroi_host_launch.h"
+#include "rroi_depthwise_host.h"
 
 }  // namespace
 
@@ -537,6 +540,22 @@ int rroi_align_backward_bucketed_hip(const rroi_align_crop* top_diffs, int dtype
         typedef decltype(tag) T;
         return launch_backward(P, static_cast<const T*>(nullptr), rois, static_cast<T*>(bottom_diff), spatial_scale, workspace,
                                workspace_bytes, stream, table);
+    });
+}
+
+// ------------------------------------------------------------------------------------
+// Depthwise 3x3 convolution of the network (header section 5): one launch, no workspace.
+// ------------------------------------------------------------------------------------
+int rroi_depthwise3x3_forward_hip(int dtype, const void* x, const void* weight, void* y, int batch_size, int channels,
+                                  int height, int width, int stride, void* stream_)
+{
+    if (!depthwise_shape_ok(dtype, batch_size, channels, height, width, stride)) return 0;
+    if (!x || !weight || !y) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_depthwise3x3(static_cast<const T*>(x), static_cast<const T*>(weight), static_cast<T*>(y), batch_size,
+                                   channels, height, width, stride, stream);
     });
 }
 

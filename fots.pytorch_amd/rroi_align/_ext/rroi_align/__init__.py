@@ -140,6 +140,9 @@ _lib.rroi_align_forward_bucketed_plan.argtypes = [_i] * 8 + [_ll] + [_i] * 3 + [
 _lib.rroi_align_backward_bucketed_plan.restype = _i
 _lib.rroi_align_backward_bucketed_plan.argtypes = [_i] * 10 + [ctypes.POINTER(_Plan)]
 PLAN_KERNEL_STRIDED_RAGGED = 5
+# the network's depthwise 3x3 convolution (header section 5; after 0.10.0, same version string: found by symbol)
+_lib.rroi_depthwise3x3_forward_hip.restype = _i
+_lib.rroi_depthwise3x3_forward_hip.argtypes = [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]
 
 EXPORTS = (
     "RROIAlignForwardLaucher", "RROIAlignBackwardLaucher", "rroi_align_forward_hip",
@@ -159,6 +162,7 @@ EXPORTS = (
     "rroi_align_forward_bucketed_hip", "rroi_align_backward_bucketed_hip",
     "rroi_align_forward_bucketed_plan", "rroi_align_backward_bucketed_plan",
     "rroi_align_forward_bucketed_workspace_bytes", "rroi_align_backward_bucketed_workspace_bytes",
+    "rroi_depthwise3x3_forward_hip",
 )
 
 # What a call launches (rroi_align_forward_plan / rroi_align_backward_plan); the fields of rroi_align_plan.
@@ -617,6 +621,52 @@ def backward_bucketed(grads, rois: torch.Tensor, feature_size, pooled_height: in
                                                    grad_in.data_ptr(), ws.data_ptr(), nbytes, word, _stream())
     _check(st, "rroi_align_backward_bucketed_hip")
     return grad_in
+
+
+# --------------------------------------------------------------------------- depthwise 3x3 (header section 5)
+def depthwise3x3(x: torch.Tensor, weight: torch.Tensor, stride: int = 1) -> torch.Tensor:
+    """(N,C,H,W) x (C,1,3,3) -> (N,C,Ho,Wo): depthwise 3x3 convolution, padding 1, no bias, stride 1 or 2.
+    float32, bfloat16 or float16, x and weight alike; x is made NCHW-contiguous.  Every output is the double sum of its
+    nine widened products in (ky, kx) order, rounded to fp32 once and then to the tensors' type: the same bits on every
+    run.  Forward only (no autograd).  ValueError for mismatched shapes or dtypes, RuntimeError for CPU tensors."""
+    if not isinstance(x, torch.Tensor) or not isinstance(weight, torch.Tensor):
+        raise TypeError("x and weight must be torch.Tensors")
+    if x.dim() != 4:
+        raise ValueError(f"x must be (N,C,H,W), got {tuple(x.shape)}")
+    N, C, H, W = x.shape
+    if tuple(weight.shape) != (C, 1, 3, 3):
+        raise ValueError(f"weight must be {(C, 1, 3, 3)} for x {tuple(x.shape)}, got {tuple(weight.shape)}")
+    if weight.dtype != x.dtype:
+        raise ValueError(f"x and weight must have one dtype, got {x.dtype} and {weight.dtype}")
+    if stride not in (1, 2):
+        raise ValueError(f"stride must be 1 or 2, got {stride!r}")
+    _require_cuda_f32(x, "x", _IO_DTYPES)
+    _require_cuda_f32(weight, "weight", _IO_DTYPES)
+    if weight.device != x.device:
+        raise ValueError("x and weight must be on the same device")
+    if C < 1 or H < 1 or W < 1:
+        raise ValueError(f"x must have at least one channel, row and column, got {tuple(x.shape)}")
+    return _depthwise3x3_run(x.contiguous(), weight, int(stride))
+
+
+def _depthwise3x3_run(x: torch.Tensor, weight: torch.Tensor, stride: int) -> torch.Tensor:
+    """The call itself, for arguments already checked (depthwise3x3 above; fots_e2e.native after native_ok): x is a
+    contiguous CUDA (N,C,H,W) tensor, weight (C,1,3,3) of its dtype and device, stride 1 or 2.  Kept lean: a network pass
+    makes 22 of these calls and the one-image leg of the pipeline is bound by host time."""
+    N, C, H, W = x.shape
+    weight = weight.contiguous()
+    index = x.device.index
+    if index != torch.cuda.current_device():
+        with torch.cuda.device(index):
+            return _depthwise3x3_run(x, weight, stride)
+    out = torch.empty((N, C, (H - 1) // stride + 1, (W - 1) // stride + 1), dtype=x.dtype, device=x.device)
+    if N == 0:
+        return out
+    st = _lib.rroi_depthwise3x3_forward_hip(_DTYPES[x.dtype], x.data_ptr(), weight.data_ptr(), out.data_ptr(), N, C, H, W,
+                                            stride, _stream())
+    if st != 1:
+        _check(st, "rroi_depthwise3x3_forward_hip")
+    return out
 
 
 def bin_centres(rois: torch.Tensor, pooled_height: int, pooled_width: int, spatial_scale: float,

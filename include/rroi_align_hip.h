@@ -472,6 +472,32 @@ int rroi_ctc_greedy_decode_hip(const float* logits, int num_seqs, int num_classe
 int rroi_ctc_greedy_decode_typed_hip(int dtype, const void* logits, int num_seqs, int num_classes, int num_steps,
                                      const int* lengths, int* labels, int* decoded, int* decoded_len, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * 5. The network's depthwise 3x3 convolution, replacing the stock convolution behind
+ *    tools/models.py:70-102 (conv_dw_plain, conv_dw_in, conv_dw_res: `nn.Conv2d(c, c, 3, stride, 1, groups=c,
+ *    bias=False)`) -- the depthwise halves of the separable blocks of layer3 / layer4 and of upconv1 / upconv2.
+ *    Forward only; opt-in from Python (fots_e2e.native.use_native_depthwise).
+ *
+ *      x      (N, C, H, W)   contiguous NCHW, element type `dtype` (RROI_DTYPE_*)
+ *      weight (C, 1, 3, 3)   contiguous, the same element type
+ *      y      (N, C, Ho, Wo) Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1; EVERY element is written and
+ *                            nothing else is
+ *    padding 1, dilation 1, no bias, stride 1 or 2 on both axes.  Arithmetic, fixed so that results compare as bits:
+ *      acc = +0.0 (double); for ky = 0, 1, 2: for kx = 0, 1, 2 (this order):
+ *          acc = acc + (double)weight[c, 0, ky, kx] * (double)(inside the image ? x[n, c, oy * stride - 1 + ky,
+ *                                                                                   ox * stride - 1 + kx] : +0.0)
+ *      y[n, c, oy, ox] = (T)(float)acc
+ *    -- a 16-bit element is widened exactly where it is loaded, the sum is rounded to fp32 once and (16-bit types)
+ *    converted once more, to nearest even, NaN kept; a tap outside the image is weight * (+0.0), never skipped (NaN for
+ *    a non-finite weight, as zero padding gives); fp32 subnormals are kept on input and output.
+ *    Any element-aligned x, weight and y work (a view one element into an allocation is a legal argument).
+ *    Returns 1 / 0 / -hipError.  0, before any launch: an unknown dtype, a stride other than 1 or 2, a dimension below
+ *    1, a NULL pointer, N * C * H * W >= 2^31.  The call only enqueues one kernel on `stream`, allocates nothing and can
+ *    be captured into a HIP graph.  Arrived after 0.10.0 under the same version string: detect it by symbol.
+ * ------------------------------------------------------------------------- */
+int rroi_depthwise3x3_forward_hip(int dtype, const void* x, const void* weight, void* y, int batch_size, int channels,
+                                  int height, int width, int stride, void* stream);
+
 /* Bin centres only: geom (R, PH, PW, 2) = (bin_cx, bin_cy), 0 where the bin is
  * outside the ROI's pooled width (kernel.cu:86-107).  Diagnostic / test hook. */
 int rroi_align_bin_centres_hip(float spatial_scale, int num_rois, int height, int width,
@@ -501,7 +527,8 @@ int rroi_align_get_trig_recipe_hip(void);
 
 /* Identification: "rroi_align_hip <version> gfx950" (0.7.0: per-call trig recipe, device-wide setter removed; 0.8.0: launcher scratch reused within a capture, table of 64, stats; 0.9.0: plan query; 0.10.0: bfloat16 / float16 tensors).
  * The typed callers' entry points (rroi_rbox_decode_typed_hip, rroi_ctc_greedy_decode_typed_hip) arrived after 0.10.0 under
- * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b. */
+ * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b and the depthwise
+ * convolution of section 5. */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
