@@ -27,8 +27,8 @@
 // geometry recipe, descriptor helpers), rroi_forward_kernels.h, rroi_backward_kernels.h, rroi_backward_tile_kernels.h,
 // rroi_callers_kernels.h, rroi_nms_kernels.h (+ rroi_nms_host.h, host C++), rroi_depthwise_kernels.h (+ rroi_depthwise_host.h:
 // the network's depthwise 3x3 convolution).  Host side: rroi_host_plan.h (tuning table,
-// Shape, limits, workspace carvers, the dispatch), rroi_host_scratch.h (the launchers' scratch), rroi_host_launch.h
-// (the launches).
+// Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
+// launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -438,12 +438,8 @@ int rroi_align_forward_plan_typed(int dtype, int feature_layout, int top_layout,
                                   int width, int channels, int pooled_height, int pooled_width, int path, int caller,
                                   rroi_align_plan* plan)
 {
-    if (!plan) return 0;
     const Shape S{batch_size, num_rois, height, width, channels, pooled_height, pooled_width};
-    const FwdDispatch P = plan_forward(S, feature_layout, top_layout, path, caller, dtype);
-    if (!P.status) return 0;
-    *plan = to_plan(P);
-    return 1;
+    return report_plan(plan_forward(S, feature_layout, top_layout, path, caller, dtype), plan);
 }
 
 int rroi_align_backward_plan(int top_diff_layout, int bottom_diff_layout, int batch_size, int num_rois, int height,
@@ -458,12 +454,8 @@ int rroi_align_backward_plan_typed(int dtype, int top_diff_layout, int bottom_di
                                    int height, int width, int channels, int pooled_height, int pooled_width, int path,
                                    int caller, rroi_align_plan* plan)
 {
-    if (!plan) return 0;
     const Shape S{batch_size, num_rois, height, width, channels, pooled_height, pooled_width};
-    const BwdDispatch P = plan_backward(S, top_diff_layout, bottom_diff_layout, path, caller, dtype);
-    if (!P.status) return 0;
-    *plan = to_plan(P);
-    return 1;
+    return report_plan(plan_backward(S, top_diff_layout, bottom_diff_layout, path, caller, dtype), plan);
 }
 
 // ------------------------------------------------------------------------------------
@@ -484,23 +476,15 @@ int rroi_align_forward_bucketed_plan(int dtype, int batch_size, int num_rois, in
                                      int pooled_height, int max_pooled_width, long long sum_pooled_widths, int width_multiple,
                                      int crop_alignment, int path, rroi_align_plan* plan)
 {
-    if (!plan) return 0;
     const Shape S{batch_size, num_rois, height, width, channels, pooled_height, max_pooled_width};
-    const FwdDispatch P = plan_forward_bucketed(S, dtype, sum_pooled_widths, width_multiple, crop_alignment, path);
-    if (!P.status) return 0;
-    *plan = to_plan(P);
-    return 1;
+    return report_plan(plan_forward_bucketed(S, dtype, sum_pooled_widths, width_multiple, crop_alignment, path), plan);
 }
 
 int rroi_align_backward_bucketed_plan(int dtype, int bottom_diff_layout, int batch_size, int num_rois, int height, int width,
                                       int channels, int pooled_height, int max_pooled_width, int path, rroi_align_plan* plan)
 {
-    if (!plan) return 0;
     const Shape S{batch_size, num_rois, height, width, channels, pooled_height, max_pooled_width};
-    const BwdDispatch P = plan_backward(S, RROI_LAYOUT_NCHW, bottom_diff_layout, path, RROI_CALLER_NATIVE, dtype, /*ragged*/ true);
-    if (!P.status) return 0;
-    *plan = to_plan(P);
-    return 1;
+    return report_plan(plan_backward(S, RROI_LAYOUT_NCHW, bottom_diff_layout, path, RROI_CALLER_NATIVE, dtype, /*ragged*/ true), plan);
 }
 
 int rroi_align_forward_bucketed_hip(const void* features, int dtype, float spatial_scale, int batch_size, int num_rois,

@@ -1,6 +1,10 @@
 // rroi_host_launch.h -- host side, part 3 of 3: the launches.  Every launch_* runs the plan it is handed (rroi_host_plan.h) on
-// the Shape that plan carries, so a launch cannot run on another shape than its plan.  Plain templates over the element
-// type T of the caller's tensors (float, bf16_t, fp16_t).  Included by rroi_align_hip.hip inside its anonymous namespace.
+// the Shape that plan carries, so a launch cannot run on another shape than its plan.  Nothing here looks at the device or
+// at the tuning table: every grid, block count and flag word is a field of the plan; what a launch derives itself is a
+// pure function of the Shape (row pitch, layouts, memset sizes).  Each kernel template has ONE function that writes its
+// argument list; runtime values become template arguments through with_dtype / with_flag / with_choice.  Plain templates
+// over the element type T of the caller's tensors (float, bf16_t, fp16_t).  Included by rroi_align_hip.hip inside its
+// anonymous namespace.
 #pragma once
 
 inline int status_of(hipError_t e) { return e == hipSuccess ? 1 : -(int)e; }
@@ -11,6 +15,21 @@ template <class F>
 auto with_dtype(int dtype, F&& f)
 {
     return dtype == RROI_DTYPE_BF16 ? f(bf16_t{}) : dtype == RROI_DTYPE_FP16 ? f(fp16_t{}) : f(float{});
+}
+// f(std::true_type{}) or f(std::false_type{}): a runtime flag as a template argument
+template <class F>
+auto with_flag(bool flag, F&& f)
+{
+    return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+template <int V>
+using int_c = std::integral_constant<int, V>;
+// f(int_c<V>{}) for the V that `v` equals; the last V stands for every other value
+template <int V, int... Rest, class F>
+auto with_choice(int v, F&& f)
+{
+    if constexpr (sizeof...(Rest) == 0) return f(int_c<V>{});
+    else return v == V ? f(int_c<V>{}) : with_choice<Rest...>(v, f);
 }
 
 // Where the forward gather finds a pixel's 32 channels (SliceLayout, rroi_device_common.h).  The chunk-major copy of the
@@ -64,26 +83,38 @@ ListAddressing list_addressing(const Shape& S, bool td_nhwc)
             make_fastdiv((unsigned)S.pooled_width), make_patch_map(S.pooled_height, S.pooled_width)};
 }
 
-template <class T>
-void launch_patch_forward(const FwdDispatch& P, const T* features, const float* rois, T* top_data, float* idx_x, float* idx_y,
-                          float spatial_scale, hipStream_t stream)
+// ------------------------------------------------------------------------------------
+// Forward.
+// ------------------------------------------------------------------------------------
+// rroi_fwd_patch_kernel<4, WITH_IDX, T, RAGGED> (K2p).  `out`: the crops, or RAGGED the crop table.
+template <bool WITH_IDX, class T, bool RAGGED = false>
+void launch_patch_kernel(const FwdDispatch& P, const T* features, const float* rois,
+                         std::conditional_t<RAGGED, const CropRow*, T*> out, float* idx_x, float* idx_y, float spatial_scale,
+                         hipStream_t stream)
 {
+    static_assert(!WITH_IDX || (std::is_same<T, float>::value && !RAGGED), "con_idx: the reference ABI's, fp32 calls only");
     const PatchPlan& p = P.patch;
     const Shape& S = P.shape;
-    const int num_rois = S.num_rois, channels = S.channels, height = S.height, width = S.width;
-    const int pooled_height = S.pooled_height, pooled_width = S.pooled_width, trig = P.trig, batch_size = P.direct_batch();
-    if constexpr (!std::is_same<T, float>::value)   // (the reference ABI's con_idx: fp32 calls only)
-        hipLaunchKernelGGL((rroi_fwd_patch_kernel<4, false, T>), p.grid, dim3(256), 0, stream, features, rois, top_data, num_rois,
-                           channels, height, width, pooled_height, pooled_width, spatial_scale, trig, batch_size, p.cw, p.npx,
-                           p.npatches, p.prows, p.pcols, (float*)nullptr, (float*)nullptr);
-    else if (idx_x)
-        hipLaunchKernelGGL((rroi_fwd_patch_kernel<4, true>), p.grid, dim3(256), 0, stream, features, rois, top_data, num_rois, channels,
-                           height, width, pooled_height, pooled_width, spatial_scale, trig, batch_size, p.cw, p.npx, p.npatches,
-                           p.prows, p.pcols, idx_x, idx_y);
-    else
-        hipLaunchKernelGGL((rroi_fwd_patch_kernel<4, false>), p.grid, dim3(256), 0, stream, features, rois, top_data, num_rois, channels,
-                           height, width, pooled_height, pooled_width, spatial_scale, trig, batch_size, p.cw, p.npx, p.npatches,
-                           p.prows, p.pcols, (float*)nullptr, (float*)nullptr);
+    hipLaunchKernelGGL((rroi_fwd_patch_kernel<4, WITH_IDX, T, RAGGED>), p.grid, dim3(256), 0, stream, features, rois, out,
+                       S.num_rois, S.channels, S.height, S.width, S.pooled_height, S.pooled_width, spatial_scale, P.trig,
+                       P.direct_batch(), p.cw, p.npx, p.npatches, p.prows, p.pcols, idx_x, idx_y);
+}
+
+// rroi_fwd_split_kernel<VEC_STORE = true, EARLY, OCC, HID, ONHWC, SHIFT, NCHW_SRC, WAUX, TO, RAGGED>.  Its three callers
+// differ in where the map is (`map`, `lay`), where the affines come from (`aff`; NCHW_SRC: `rsrc`), what `out` is (crops of
+// TO; RAGGED: the crop table) and the XCD groups.
+template <int EARLY, int OCC, int HID, bool ONHWC, int SHIFT, int WAUX, class TO, bool NCHW_SRC = false, bool RAGGED = false>
+void launch_split_kernel(const FwdDispatch& P, const float* map, const SliceLayout& lay, const Affine* aff,
+                         std::conditional_t<RAGGED, const CropRow*, TO*> out, XcdGroups xg, hipStream_t stream,
+                         RoiSource rsrc = RoiSource{nullptr, 0, 0.0f, 0})
+{
+    static_assert(!NCHW_SRC || (std::is_same<TO, float>::value && !RAGGED), "the one-launch forms are fp32 only");
+    const ForwardPlan& plan = P.gather;
+    const Shape& S = P.shape;
+    hipLaunchKernelGGL((rroi_fwd_split_kernel<true, EARLY, OCC, HID, ONHWC, SHIFT, NCHW_SRC, WAUX, TO, RAGGED>), dim3(plan.grid),
+                       dim3(2 * kWave), 0, stream, map, aff, out, S.num_rois, S.channels, S.height, S.width, S.pooled_width,
+                       S.NB(), S.batch_size, S.nchunks(), plan.ntiles, lay, make_fastdiv((unsigned)plan.ntiles),
+                       make_fastdiv((unsigned)S.pooled_width), plan.dbg, xg, rsrc);
 }
 
 // The forward prologue launch (relayout to the chunk-major copy + affine table [+ ROI sort, + the launcher's rest blocks]):
@@ -92,31 +123,15 @@ template <class T>
 int launch_forward_prologue(const FwdDispatch& P, const Workspace& ws, const T* features, const float* rois, T* top_data,
                             float spatial_scale, hipStream_t stream)
 {
-    constexpr bool kF32 = std::is_same<T, float>::value;
     const Shape& S = P.shape;
-    const int batch_size = S.batch_size, num_rois = S.num_rois, width = S.width, channels = S.channels;
-    const int HW = S.HW(), nchunks = S.nchunks(), groups = P.groups;
-    const bool zero_copy = P.zero_copy, launcher_rest = P.launcher;
-    const int pitch = row_pitch(width);
-    const int ptiles = ceil_div(HW, kRelayoutPx);
-    const int relayout_tiles = zero_copy ? 0 : ptiles * nchunks * batch_size;
-    // ~3 resident blocks per CU, each streaming several tiles with the next tile prefetched
-    int relayout_blocks = relayout_tiles;
-    if (groups > 1) relayout_blocks = (relayout_blocks + 7) / 8 * 8;   // whole XCD rounds (a block without a tile leaves)
-    if (relayout_blocks > num_cus() * g_tune.prologue_blocks_per_cu) {
-        relayout_blocks = num_cus() * g_tune.prologue_blocks_per_cu;
-        const long unit = lcm8(nchunks);   // keeps block -> chunk -> XCD stable
-        if (relayout_blocks >= unit) relayout_blocks = (int)(relayout_blocks / unit * unit);
-    }
-    const int aff_blocks = ceil_div(num_rois, 256);
-    const int rest_blocks = launcher_rest ? num_rois : 0;
+    const ProloguePlan& p = P.prologue;
     float* rest_out = nullptr;   // (the launcher: fp32)
-    if constexpr (kF32) rest_out = launcher_rest ? top_data : nullptr;
+    if constexpr (std::is_same<T, float>::value) rest_out = P.launcher ? top_data : nullptr;
     // <0>: plain stores: the copy stays in the L2s that wrote it (write-through: 1.8 us faster alone, the step is not)
-    hipLaunchKernelGGL((rroi_prologue_kernel<0, T>), dim3(relayout_blocks + aff_blocks + (groups > 1 ? 1 : 0) + rest_blocks),
-                       dim3(256), 0, stream, features, ws.cm, channels, HW, width, pitch, make_fastdiv((unsigned)width), nchunks,
-                       ptiles, relayout_blocks, relayout_tiles, batch_size, rois, num_rois, S.pooled_height, spatial_scale,
-                       P.trig, ws.aff, aff_blocks, rest_out, S.pooled_width, groups, ws.sort_rank, ws.sort_order);
+    hipLaunchKernelGGL((rroi_prologue_kernel<0, T>), dim3(p.grid()), dim3(256), 0, stream, features, ws.cm, S.channels, S.HW(),
+                       S.width, row_pitch(S.width), make_fastdiv((unsigned)S.width), S.nchunks(), p.ptiles, p.relayout_blocks,
+                       p.relayout_tiles, S.batch_size, rois, S.num_rois, S.pooled_height, spatial_scale, P.trig, ws.aff,
+                       p.aff_blocks, rest_out, S.pooled_width, P.groups, ws.sort_rank, ws.sort_order);
     return launch_status();
 }
 
@@ -131,43 +146,38 @@ int launch_forward(const FwdDispatch& P, const T* features, const float* rois, T
 {
     constexpr bool kF32 = std::is_same<T, float>::value;
     const Shape& S = P.shape;
-    const int batch_size = S.batch_size, num_rois = S.num_rois, height = S.height, width = S.width, channels = S.channels;
-    const int pooled_height = S.pooled_height, pooled_width = S.pooled_width, NB = S.NB(), nchunks = S.nchunks();
-    const int trig = P.trig;
     switch (P.family) {
     case RROI_PLAN_NONE:
         return 1;
     case RROI_PLAN_FWD_DIRECT_K2P:
         if (!(stages & RROI_STAGE_GATHER)) return 1;  // the direct path has no prologue
-        launch_patch_forward(P, features, rois, top_data, P.con_idx ? idx_x : nullptr, P.con_idx ? idx_y : nullptr,
-                             spatial_scale, stream);
+        if constexpr (kF32) {
+            if (P.con_idx && idx_x) {
+                launch_patch_kernel<true>(P, features, rois, top_data, idx_x, idx_y, spatial_scale, stream);
+                return launch_status();
+            }
+        }
+        launch_patch_kernel<false>(P, features, rois, top_data, nullptr, nullptr, spatial_scale, stream);
         return launch_status();
     case RROI_PLAN_FWD_DIRECT_THREAD:
         if (!(stages & RROI_STAGE_GATHER)) return 1;
         hipLaunchKernelGGL(rroi_fwd_direct_kernel<T>, P.dgrid, dim3(256), 0, stream, features, rois, top_data,
-                           P.con_idx ? idx_x : nullptr, P.con_idx ? idx_y : nullptr, num_rois, channels, height, width,
-                           pooled_height, pooled_width, spatial_scale, trig, P.direct_batch(), P.cslab);
+                           P.con_idx ? idx_x : nullptr, P.con_idx ? idx_y : nullptr, S.num_rois, S.channels, S.height, S.width,
+                           S.pooled_height, S.pooled_width, spatial_scale, P.trig, P.direct_batch(), P.cslab);
         return launch_status();
     case RROI_PLAN_FWD_FUSED_STRIDED:
-    case RROI_PLAN_FWD_FUSED_SHIFT: {
+    case RROI_PLAN_FWD_FUSED_SHIFT:
         if constexpr (!kF32) {   // (fp32 only: no 16-bit plan)
             return 0;
         } else {
-        if (!(stages & RROI_STAGE_GATHER)) return 1;  // one launch, run under the gather stage
-        const ForwardPlan& plan = P.gather;
-        const SliceLayout lay = nchw_src_layout(S);
-        const FastDiv dt = make_fastdiv((unsigned)plan.ntiles), dp = make_fastdiv((unsigned)pooled_width);
-        const RoiSource rsrc = {rois, pooled_height, spatial_scale, trig};
-#define RROI_FUSED(...)                                                                                                   \
-    hipLaunchKernelGGL((rroi_fwd_split_kernel<__VA_ARGS__>), dim3(plan.grid), dim3(2 * kWave), 0, stream, features,          \
-                       (const Affine*)nullptr, top_data, num_rois, channels, height, width, pooled_width, NB, batch_size,    \
-                       nchunks, plan.ntiles, lay, dt, dp, plan.dbg, XcdGroups{1, nullptr}, rsrc)
-        if (P.family == RROI_PLAN_FWD_FUSED_SHIFT) RROI_FUSED(true, 0, 4, 3, false, 1, true);
-        else RROI_FUSED(true, 0, 4, 3, false, 0, true);
-#undef RROI_FUSED
-        return launch_status();
+            if (!(stages & RROI_STAGE_GATHER)) return 1;  // one launch, run under the gather stage
+            const RoiSource rsrc = {rois, S.pooled_height, spatial_scale, P.trig};
+            with_flag(P.family == RROI_PLAN_FWD_FUSED_SHIFT, [&](auto shift) {
+                launch_split_kernel<0, 4, 3, false, decltype(shift)::value ? 1 : 0, -1, float, true>(
+                    P, features, nchw_src_layout(S), nullptr, top_data, XcdGroups{1, nullptr}, stream, rsrc);
+            });
+            return launch_status();
         }
-    }
     case RROI_PLAN_FWD_TWO_LAUNCH:
         break;
     default:
@@ -179,7 +189,6 @@ int launch_forward(const FwdDispatch& P, const T* features, const float* rois, T
     if (!workspace_ok(workspace) || workspace_bytes < ws.bytes) return 0;
     const float* map = ws.cm;
     if constexpr (kF32) map = zero_copy ? features : ws.cm;
-    const int groups = P.groups;
 
     // prologue: relayout + affine table in one launch
     if (stages & RROI_STAGE_PROLOGUE) {
@@ -187,25 +196,17 @@ int launch_forward(const FwdDispatch& P, const T* features, const float* rois, T
         if (st != 1) return st;
     }
     if (stages & RROI_STAGE_GATHER) {
-        const ForwardPlan& plan = P.gather;
-        const int ntiles = plan.ntiles;
         const SliceLayout lay = zero_copy ? zero_copy_layout(S) : chunk_major_layout(S);
-        const FastDiv dt = make_fastdiv((unsigned)ntiles), dp = make_fastdiv((unsigned)pooled_width);
-        // the shipped instantiations of rroi_fwd_split_kernel<VEC_STORE, EARLY, OCC, HID, ONHWC, SHIFT, NCHW_SRC, WAUX, T>,
-        // one per FwdKernel and element type
-#define RROI_GATHER(...)                                                                                              \
-    hipLaunchKernelGGL((rroi_fwd_split_kernel<__VA_ARGS__>), dim3(plan.grid), dim3(2 * kWave), 0, stream, map, ws.aff, \
-                       top_data, num_rois, channels, height, width, pooled_width, NB, batch_size, nchunks, ntiles, lay, \
-                       dt, dp, plan.dbg, XcdGroups{groups, ws.sort_order})
-        switch (plan.kernel) {
-        case FwdKernel::kStrided:       RROI_GATHER(true, 0, 6, 3, false, 0, false, -1, T); break;   // 62-64 VGPRs, 12.1 KB of LDS: 12 per CU
-        case FwdKernel::kChannelsLast:  RROI_GATHER(true, 2, 5, 2, true, 0, false, -1, T); break;    // 91 VGPRs: 10 per CU
-        case FwdKernel::kShift:         RROI_GATHER(true, 0, 6, 3, false, 1, false, -1, T); break;   // 79 VGPRs, 12.4 KB of LDS: 12 per CU
-        case FwdKernel::kStridedMerge:  RROI_GATHER(true, 0, 6, 3, false, 0, false, 0, T); break;    // plain stores (write-through: 32.1 against 30.1 us)
-        case FwdKernel::kShiftLines:    RROI_GATHER(true, 0, 5, 3, false, 2, false, -1, T); break;   // 84 VGPRs, 14.8 KB of LDS: 10 per CU
+        const XcdGroups xg{P.groups, ws.sort_order};
+        // the shipped instantiations <EARLY, OCC, HID, ONHWC, SHIFT, WAUX, T>, one per FwdKernel and element type
+        switch (P.gather.kernel) {
+        case FwdKernel::kStrided:       launch_split_kernel<0, 6, 3, false, 0, -1, T>(P, map, lay, ws.aff, top_data, xg, stream); break;   // 62-64 VGPRs, 12.1 KB of LDS: 12 per CU
+        case FwdKernel::kChannelsLast:  launch_split_kernel<2, 5, 2, true, 0, -1, T>(P, map, lay, ws.aff, top_data, xg, stream); break;    // 91 VGPRs: 10 per CU
+        case FwdKernel::kShift:         launch_split_kernel<0, 6, 3, false, 1, -1, T>(P, map, lay, ws.aff, top_data, xg, stream); break;   // 79 VGPRs, 12.4 KB of LDS: 12 per CU
+        case FwdKernel::kStridedMerge:  launch_split_kernel<0, 6, 3, false, 0, 0, T>(P, map, lay, ws.aff, top_data, xg, stream); break;    // plain stores (write-through: 32.1 against 30.1 us)
+        case FwdKernel::kShiftLines:    launch_split_kernel<0, 5, 3, false, 2, -1, T>(P, map, lay, ws.aff, top_data, xg, stream); break;   // 84 VGPRs, 14.8 KB of LDS: 10 per CU
         case FwdKernel::kStridedRagged: return 0;   // (launch_forward_bucketed's own)
         }
-#undef RROI_GATHER
     }
     return launch_status();
 }
@@ -214,14 +215,9 @@ template <class T>
 int launch_forward_bucketed(const FwdDispatch& P, const T* features, const float* rois, const CropRow* crops,
                             float spatial_scale, void* workspace, size_t workspace_bytes, hipStream_t stream)
 {
-    const Shape& S = P.shape;
-    const int batch_size = S.batch_size, num_rois = S.num_rois, height = S.height, width = S.width, channels = S.channels;
-    const int pooled_height = S.pooled_height, max_pooled_width = S.pooled_width, nchunks = S.nchunks();
+    const Shape& S = P.shape;   // (pooled_width: the call's largest)
     if (P.family == RROI_PLAN_FWD_DIRECT_K2P) {
-        const PatchPlan& p = P.patch;
-        hipLaunchKernelGGL((rroi_fwd_patch_kernel<4, false, T, true>), p.grid, dim3(256), 0, stream, features, rois, crops,
-                           num_rois, channels, height, width, pooled_height, max_pooled_width, spatial_scale, P.trig, batch_size,
-                           p.cw, p.npx, p.npatches, p.prows, p.pcols, (float*)nullptr, (float*)nullptr);
+        launch_patch_kernel<false, T, true>(P, features, rois, crops, nullptr, nullptr, spatial_scale, stream);
         return launch_status();
     }
     if (P.family != RROI_PLAN_FWD_TWO_LAUNCH) return 0;
@@ -229,13 +225,186 @@ int launch_forward_bucketed(const FwdDispatch& P, const T* features, const float
     if (!workspace_ok(workspace) || workspace_bytes < ws.bytes) return 0;
     const int st = launch_forward_prologue(P, ws, features, rois, (T*)nullptr, spatial_scale, stream);
     if (st != 1) return st;
-    const SliceLayout lay = chunk_major_layout(S);
-    const ForwardPlan& plan = P.gather;
-    const FastDiv dt = make_fastdiv((unsigned)plan.ntiles), dp = make_fastdiv((unsigned)max_pooled_width);
-    hipLaunchKernelGGL((rroi_fwd_split_kernel<true, 0, 6, 3, false, 0, false, -1, T, true>), dim3(plan.grid), dim3(2 * kWave), 0,
-                       stream, ws.cm, ws.aff, crops, num_rois, channels, height, width, max_pooled_width,
-                       pooled_height * max_pooled_width, batch_size, nchunks, plan.ntiles, lay, dt, dp, plan.dbg,
-                       XcdGroups{1, nullptr}, RoiSource{nullptr, 0, 0.0f, 0});
+    launch_split_kernel<0, 6, 3, false, 0, -1, T, false, true>(P, ws.cm, chunk_major_layout(S), ws.aff, crops,
+                                                               XcdGroups{1, nullptr}, stream);
+    return launch_status();
+}
+
+// ------------------------------------------------------------------------------------
+// Backward.
+// ------------------------------------------------------------------------------------
+// What the launches of one tiled backward call share, and one method per kernel template they run.
+template <class T>
+struct BwdLaunch {
+    static constexpr bool kF32 = std::is_same<T, float>::value;
+    const BwdDispatch& P;
+    const Shape& S;
+    BwdWorkspace ws;          // the caller's workspace, carved
+    ListAddressing A;
+    const float* srcT;        // where the gather reads top_diff: the relaid-out fp32 copy, or an fp32 channels-last top_diff in place
+    const T* top_diff;        // the gradient crops, or ...
+    const CropRow* ragged;    // ... the bucketed call: their table (top_diff is NULL)
+    T* bottom_diff;
+    hipStream_t stream;
+
+    // bucket lists: the chains' heads in `off`, the overflow counter in `bsum`
+    BucketLists bucket_lists() const { return {ws.kshift, reinterpret_cast<int*>(ws.off), ws.bsum, ws.ov}; }
+    FastDiv div_key_tiles() const { return make_fastdiv(ws.keys.Ht * ws.keys.Wt); }
+
+    // rroi_bwd_pairs_relayout_kernel<MODE, kBwdRelayoutAux, T, RAGGED>: `pair_blocks` pair blocks (MODE 0 count, 1 fill,
+    // 2 buckets) in front of `blocks` blocks that relay out the tiles [tile_begin, tile_end) of top_diff
+    template <int MODE>
+    void pairs_relayout(int pair_blocks, int tt, long blocks, long tile_begin, long tile_end, int raw_bsum, const BucketLists& bl,
+                        int flags) const
+    {
+        auto run = [&](auto is_ragged, auto src) {
+            hipLaunchKernelGGL((rroi_bwd_pairs_relayout_kernel<MODE, kBwdRelayoutAux, T, decltype(is_ragged)::value>),
+                               dim3((unsigned)(pair_blocks + blocks)), dim3(256), 0, stream, ws.aff, S.num_rois, S.height, S.width,
+                               S.pooled_width, S.NB(), S.batch_size, A.lines_per_roi, A.dnb, A.dpw, ws.keys, ws.cnt, ws.off,
+                               ws.bsum, ws.pairs, pair_blocks, src, ws.tdT, S.channels, S.nchunks(), tt, (int)blocks,
+                               (int)tile_begin, (int)tile_end, ws.scan_blocks, raw_bsum, bl, flags);
+        };
+        if (ragged) run(std::true_type{}, ragged);
+        else run(std::false_type{}, top_diff);
+    }
+
+    // rroi_bwd_tile_gather_kernel<NK, NHWC, TO>.  NHWC: the caller's bottom_diff in place (its type); else the fp32
+    // chunk-major scratch.  A 16-bit call has no eight-chunk instantiation (plan_backward: nk <= 4).
+    void tile_gather() const
+    {
+        auto run = [&](auto nk, auto nhwc) {
+            constexpr bool kNhwc = decltype(nhwc)::value;
+            typedef std::conditional_t<kNhwc, T, float> TO;
+            TO* dst;
+            if constexpr (kNhwc) dst = bottom_diff;
+            else dst = ws.gcm;
+            hipLaunchKernelGGL((rroi_bwd_tile_gather_kernel<decltype(nk)::value, kNhwc, TO>), P.grid, dim3(kTgThreads), 0, stream,
+                               srcT, ws.aff, dst, S.num_rois, S.channels, S.height, S.width, row_pitch(S.width), S.pooled_height,
+                               S.pooled_width, S.batch_size, S.nchunks(), A.chunk_stride, A.line_stride, A.lines_per_roi, ws.keys,
+                               ws.keys.keys / 32u, P.grid.x / 8u, div_key_tiles(), make_fastdiv(ws.keys.Wt),
+                               make_fastdiv((unsigned)S.pooled_height));
+        };
+        with_flag(P.dest == RROI_PLAN_DST_NHWC, [&](auto nhwc) {
+            if constexpr (kF32) with_choice<8, 4, 2, 1>(P.inkernel.nk, [&](auto nk) { run(nk, nhwc); });
+            else with_choice<4, 2, 1>(P.inkernel.nk, [&](auto nk) { run(nk, nhwc); });
+        });
+    }
+
+    // rroi_bwd_gather_kernel<DST, BUCKET, TO>: the lists are count / scan / fill segments (`off` = scanned offsets) or
+    // buckets (`off` = the counters).  kDstNchwAdd (the launcher's) is fp32 only.
+    void list_gather() const
+    {
+        const bool buckets = P.family == RROI_PLAN_BWD_BUCKETS;
+        const unsigned* loff = buckets ? reinterpret_cast<const unsigned*>(ws.cnt) : ws.off;
+        with_flag(buckets, [&](auto buck) {
+            auto run = [&](auto dstk, auto* dst) {
+                hipLaunchKernelGGL((rroi_bwd_gather_kernel<decltype(dstk)::value, decltype(buck)::value, std::remove_pointer_t<decltype(dst)>>),
+                                   P.grid, dim3(256), 0, stream, srcT, loff, ws.bsum, ws.pairs, dst, S.channels, S.height, S.width,
+                                   row_pitch(S.width), S.nchunks(), A.chunk_stride, A.line_stride, P.lists.sub_shift, ws.keys,
+                                   div_key_tiles(), make_fastdiv(ws.keys.Wt), ws.scan_blocks, P.lists.raw_bsum, bucket_lists(),
+                                   P.lists.tile_run);
+            };
+            switch (P.dest) {
+            case RROI_PLAN_DST_NHWC: run(int_c<kDstNhwc>{}, bottom_diff); break;
+            case RROI_PLAN_DST_NCHW: run(int_c<kDstNchw>{}, bottom_diff); break;
+            case RROI_PLAN_DST_NCHW_ADD: if constexpr (kF32) run(int_c<kDstNchwAdd>{}, bottom_diff); break;
+            default: run(int_c<kDstChunkMajor>{}, ws.gcm); break;
+            }
+        });
+    }
+
+    // rroi_bwd_ordered_gather_kernel<kDstNhwc | kDstNchw, T>: in place, in either layout
+    void ordered_gather() const
+    {
+        with_flag(P.dest == RROI_PLAN_DST_NHWC, [&](auto nhwc) {
+            constexpr int kDst = decltype(nhwc)::value ? kDstNhwc : kDstNchw;
+            hipLaunchKernelGGL((rroi_bwd_ordered_gather_kernel<kDst, T>), P.grid, dim3(256), 0, stream, srcT, ws.off, ws.bsum,
+                               ws.pairs, bottom_diff, S.channels, S.height, S.width, S.nchunks(), A.chunk_stride, A.line_stride,
+                               P.lists.sub_shift, ws.keys, div_key_tiles(), make_fastdiv(ws.keys.Wt), ws.scan_blocks,
+                               P.lists.raw_bsum, P.lists.tile_run);
+        });
+    }
+
+    // rroi_cm_to_nchw_kernel<ACCUM, T>: the chunk-major scratch to the caller's NCHW bottom_diff (= ; the launcher, fp32: +=)
+    void cm_to_nchw() const
+    {
+        const int ptiles = ceil_div((long)S.HW(), kRelayoutPx);
+        with_flag(P.accumulate, [&](auto accum) {
+            if constexpr (!decltype(accum)::value || kF32)
+                hipLaunchKernelGGL((rroi_cm_to_nchw_kernel<decltype(accum)::value, T>), dim3(ptiles * S.nchunks() * S.batch_size),
+                                   dim3(256), 0, stream, ws.gcm, bottom_diff, S.channels, S.HW(), S.width, row_pitch(S.width),
+                                   make_fastdiv((unsigned)S.width), S.nchunks(), ptiles);
+        });
+    }
+};
+
+// K3t: relayout of top_diff (one launch, masked bins skipped), then the tile gather
+template <class T>
+int launch_bwd_inkernel(const BwdLaunch<T>& c)
+{
+    const BwdDispatch::InKernel& K = c.P.inkernel;
+    if (!c.P.td_nhwc) {
+        c.template pairs_relayout<0>(0, K.tt, K.relayout_blocks, 0, K.tiles, 0, BucketLists{0u, nullptr, nullptr, nullptr}, K.flags);
+        const int st = launch_status();
+        if (st != 1) return st;
+    }
+    c.tile_gather();
+    return launch_status();
+}
+
+// K3g: the pixel -> (bin, weight) lists in HBM, then a gather that walks them
+template <class T>
+int launch_bwd_lists(const BwdLaunch<T>& c)
+{
+    const BwdDispatch::Lists& L = c.P.lists;
+    const BwdWorkspace& ws = c.ws;
+    const BucketLists bl = c.bucket_lists();
+    // (1) the lists
+    if (c.P.family == RROI_PLAN_BWD_BUCKETS) {
+        // ONE launch: every pair into its pixel's bucket (or overflow chain) || the whole relayout
+        c.template pairs_relayout<2>(L.pblocks, L.tt, L.bucket_blocks, 0, L.tiles, L.raw_bsum, bl, L.flags);
+    } else {
+        // count || first half of the relayout;  scan;  fill || second half
+        c.template pairs_relayout<0>(L.pblocks, L.tt, L.count_blocks, 0, L.half, L.raw_bsum, bl, L.flags);
+        hipLaunchKernelGGL(rroi_scan1_kernel, dim3(ws.scan_blocks), dim3(1024), 0, c.stream, ws.cnt, ws.off, ws.bsum,
+                           ws.keys.keys);
+        if (!L.raw_bsum) hipLaunchKernelGGL(rroi_scan2_kernel, dim3(1), dim3(1024), 0, c.stream, ws.bsum, ws.scan_blocks);
+        c.template pairs_relayout<1>(L.pblocks, L.tt, L.fill_blocks, L.half, L.tiles, L.raw_bsum, bl, L.flags);
+    }
+    const int st = launch_status();
+    if (st != 1) return st;
+    // (2) gather: one thread group per key, no grid-stride
+    if (c.P.family != RROI_PLAN_BWD_ORDERED) {
+        c.list_gather();
+        return launch_status();
+    }
+    // (2b) every list in bin order: the short ones in registers, the rest queued in the counters (which the
+    // fill left at zero) for one workgroup each; then the in-order fp64 gather, in place
+    unsigned* const queue = reinterpret_cast<unsigned*>(ws.cnt);
+    hipLaunchKernelGGL(rroi_bwd_sort_lists_kernel, dim3(L.sort_lists_blocks), dim3(256), 0, c.stream, ws.off, ws.bsum, ws.pairs,
+                       ws.keys.keys, ws.scan_blocks, L.raw_bsum, queue);
+    hipLaunchKernelGGL(rroi_bwd_sort_queue_kernel, dim3(L.sort_queue_blocks), dim3(kSortQueueThreads), 0, c.stream, ws.off,
+                       ws.bsum, ws.pairs, queue, ws.scan_blocks, L.raw_bsum);
+    c.ordered_gather();
+    return launch_status();
+}
+
+// rroi_bwd_tiled_kernel<VEC_LOAD>: the atomic scatter into the zeroed chunk-major scratch.  fp32 atomics: there is no 16-bit
+// plan, and launch_backward has refused one
+template <class T>
+int launch_bwd_atomic(const BwdLaunch<T>& c)
+{
+    const Shape& S = c.S;
+    const int pitch = row_pitch(S.width), ntiles = c.P.atomic.ntiles;
+    const hipError_t e = hipMemsetAsync(c.ws.gcm, 0, (size_t)S.batch_size * S.nchunks() * S.height * pitch * kLineBytes, c.stream);
+    if (e != hipSuccess) return status_of(e);
+    if constexpr (BwdLaunch<T>::kF32)
+        with_flag(c.P.atomic.vec4, [&](auto vec4) {
+            hipLaunchKernelGGL(rroi_bwd_tiled_kernel<decltype(vec4)::value>, c.P.grid, dim3(kWave), 0, c.stream, c.top_diff,
+                               c.ws.aff, c.ws.gcm, S.num_rois, S.channels, S.height, S.width, pitch, S.pooled_width, S.NB(),
+                               S.batch_size, S.nchunks(), ntiles, make_fastdiv((unsigned)ntiles),
+                               make_fastdiv((unsigned)S.pooled_width));
+        });
     return launch_status();
 }
 
@@ -248,27 +417,22 @@ int launch_backward(const BwdDispatch& P, const T* top_diff, const float* rois, 
 {
     constexpr bool kF32 = std::is_same<T, float>::value;
     const Shape& S = P.shape;
-    const int batch_size = S.batch_size, num_rois = S.num_rois, height = S.height, width = S.width, channels = S.channels;
-    const int pooled_height = S.pooled_height, pooled_width = S.pooled_width, NB = S.NB(), nchunks = S.nchunks();
-    const int trig = P.trig;
-    const size_t HW = S.HW();
-    const size_t in_bytes = (size_t)batch_size * channels * HW * sizeof(T);
+    const size_t in_bytes = (size_t)S.batch_size * S.channels * (size_t)S.HW() * sizeof(T);
     const bool td_nhwc = P.td_nhwc, accumulate = P.accumulate;
     switch (P.family) {
     case RROI_PLAN_NONE:
         return accumulate ? 1 : status_of(hipMemsetAsync(bottom_diff, 0, in_bytes, stream));
-    case RROI_PLAN_BWD_DIRECT: {
+    case RROI_PLAN_BWD_DIRECT:
         if constexpr (!kF32) {   // (fp32 atomics: no 16-bit plan)
             return 0;
         } else {
-            hipError_t e = hipMemsetAsync(bottom_diff, 0, in_bytes, stream);
+            const hipError_t e = hipMemsetAsync(bottom_diff, 0, in_bytes, stream);
             if (e != hipSuccess) return status_of(e);
-            hipLaunchKernelGGL(rroi_bwd_direct_kernel, P.grid, dim3(256), 0, stream, top_diff, rois,
-                               bottom_diff, num_rois, channels, height, width, pooled_height,
-                               pooled_width, spatial_scale, trig, batch_size, P.cslab);
+            hipLaunchKernelGGL(rroi_bwd_direct_kernel, P.grid, dim3(256), 0, stream, top_diff, rois, bottom_diff, S.num_rois,
+                               S.channels, S.height, S.width, S.pooled_height, S.pooled_width, spatial_scale, P.trig,
+                               S.batch_size, P.direct.cslab);
             return launch_status();
         }
-    }
     case RROI_PLAN_BWD_ATOMIC:
     case RROI_PLAN_BWD_INKERNEL:
     case RROI_PLAN_BWD_LISTS:
@@ -279,197 +443,27 @@ int launch_backward(const BwdDispatch& P, const T* top_diff, const float* rois, 
         return 0;
     }
 
-    const BwdWorkspace ws = carve_bwd(workspace, S);
+    const bool buckets = P.family == RROI_PLAN_BWD_BUCKETS;
+    const bool lists = buckets || P.family == RROI_PLAN_BWD_ORDERED || P.family == RROI_PLAN_BWD_LISTS;
+    BwdLaunch<T> c{P, S, carve_bwd(workspace, S), list_addressing(S, td_nhwc), nullptr, top_diff, ragged, bottom_diff, stream};
+    const BwdWorkspace& ws = c.ws;
     if (!workspace_ok(workspace) || workspace_bytes < ws.bytes) return 0;
     if (!kF32 && (P.family == RROI_PLAN_BWD_ATOMIC || td_nhwc || accumulate)) return 0;
-    if (ragged && (td_nhwc || accumulate || !(P.family == RROI_PLAN_BWD_LISTS || P.family == RROI_PLAN_BWD_BUCKETS ||
-                                               P.family == RROI_PLAN_BWD_ORDERED)))
-        return 0;
-    // where the gather reads top_diff: the relaid-out fp32 copy, or an fp32 channels-last top_diff in place
-    const float* srcT = ws.tdT;
-    if constexpr (kF32) srcT = td_nhwc ? top_diff : ws.tdT;
-    const int pitch = row_pitch(width);
-    const int ptiles = ceil_div((long)HW, kRelayoutPx);
-    const bool gather = P.family != RROI_PLAN_BWD_ATOMIC;
-    const bool buckets = P.family == RROI_PLAN_BWD_BUCKETS;
-    const bool ordered = P.family == RROI_PLAN_BWD_ORDERED;
-    const bool lists = buckets || ordered || P.family == RROI_PLAN_BWD_LISTS;
-    const BucketLists BL = {ws.kshift, reinterpret_cast<int*>(ws.off), ws.bsum, ws.ov};
-    {
-        // affine table; the list passes' pixel counters (K3g) are cleared by the same launch
-        const unsigned nzero = lists ? ws.keys.keys : 0u;
-        int ablocks = ceil_div(num_rois, 256);
-        const int zblocks = nzero ? (int)std::min<long>(ceil_div((long)nzero, 1024), 2L * num_cus()) : 0;
-        if (zblocks > ablocks) ablocks = zblocks;
-        hipLaunchKernelGGL(rroi_affine_kernel, dim3(ablocks), dim3(256), 0, stream, rois, num_rois, pooled_height,
-                           spatial_scale, trig, ws.aff, ws.cnt, nzero, buckets ? BL.head : (int*)nullptr,
-                           buckets ? BL.ovcnt : (unsigned*)nullptr);
-    }
+    if (ragged && (td_nhwc || accumulate || !lists)) return 0;
+    c.srcT = ws.tdT;
+    if constexpr (kF32) c.srcT = td_nhwc ? top_diff : ws.tdT;
+
+    // affine table; the list passes' pixel counters (K3g) are cleared by the same launch
+    const BucketLists bl = c.bucket_lists();
+    hipLaunchKernelGGL(rroi_affine_kernel, dim3(P.affine_blocks), dim3(256), 0, stream, rois, S.num_rois, S.pooled_height,
+                       spatial_scale, P.trig, ws.aff, ws.cnt, lists ? ws.keys.keys : 0u, buckets ? bl.head : (int*)nullptr,
+                       buckets ? bl.ovcnt : (unsigned*)nullptr);
     int st = launch_status();
     if (st != 1) return st;
-
-    const KeyLayout KL = ws.keys;
-    const ListAddressing A = list_addressing(S, td_nhwc);
-    if (P.family == RROI_PLAN_BWD_INKERNEL) {
-        // K3t: relayout of top_diff (one launch, masked bins skipped), then the tile gather
-        if (!td_nhwc) {
-            const long blocks = P.relayout_blocks;
-            hipLaunchKernelGGL((rroi_bwd_pairs_relayout_kernel<0, kBwdRelayoutAux, T>), dim3((unsigned)blocks), dim3(256), 0,
-                               stream, ws.aff, num_rois, height, width, pooled_width, NB, batch_size, A.lines_per_roi, A.dnb,
-                               A.dpw, KL, ws.cnt, ws.off, ws.bsum, ws.pairs, 0, top_diff, ws.tdT, channels, nchunks, P.tt,
-                               (int)blocks, 0, (int)P.tiles, ws.scan_blocks, 0, BucketLists{0u, nullptr, nullptr, nullptr},
-                               g_tune.bwd_skip_dead);
-            st = launch_status();
-            if (st != 1) return st;
-        }
-        const unsigned ntiles = KL.keys / 32u;
-        const unsigned per_xcd = P.grid.x / 8u;
-        const FastDiv dbt = make_fastdiv(KL.Ht * KL.Wt), dwt = make_fastdiv(KL.Wt), dph = make_fastdiv((unsigned)pooled_height);
-        // NHWC: the caller's bottom_diff in place (its type); else the fp32 chunk-major scratch
-#define RROI_LAUNCH_TG(NK, NHWC)                                                                          \
-    hipLaunchKernelGGL((rroi_bwd_tile_gather_kernel<NK, NHWC, std::conditional_t<NHWC, T, float>>), P.grid,  \
-                       dim3(kTgThreads), 0, stream,                                                          \
-                       srcT, ws.aff, NHWC ? (std::conditional_t<NHWC, T, float>*)(void*)bottom_diff          \
-                                          : (std::conditional_t<NHWC, T, float>*)(void*)ws.gcm,              \
-                       num_rois, channels, height, width, pitch, pooled_height,                              \
-                       pooled_width, batch_size, nchunks, A.chunk_stride, A.line_stride, A.lines_per_roi,    \
-                       KL, ntiles, per_xcd, dbt, dwt, dph)
-#define RROI_LAUNCH_TG_NK(NHWC)                          \
-    do {                                                 \
-        if constexpr (kF32)   /* (16-bit: nk <= 4) */    \
-            if (P.nk == 8) {                             \
-                RROI_LAUNCH_TG(8, NHWC);                 \
-                break;                                   \
-            }                                            \
-        if (P.nk == 4) RROI_LAUNCH_TG(4, NHWC);          \
-        else if (P.nk == 2) RROI_LAUNCH_TG(2, NHWC);     \
-        else RROI_LAUNCH_TG(1, NHWC);                    \
-    } while (0)
-        if (P.dest == RROI_PLAN_DST_NHWC) {
-            RROI_LAUNCH_TG_NK(true);
-            return launch_status();  // written in place: no relayout back
-        }
-        RROI_LAUNCH_TG_NK(false);
-#undef RROI_LAUNCH_TG_NK
-#undef RROI_LAUNCH_TG
-        st = launch_status();
-        if (st != 1) return st;
-    } else
-    if (gather) {
-        // (1) pixel -> (bin, weight) lists: count, scan, fill
-        const int raw_bsum = P.raw_bsum;
-        const int pblocks = P.pblocks;
-        const bool aggregate = P.aggregate;
-        const int tt = P.tt;
-        const long tiles = P.tiles, half = P.half;
-#define RROI_LAUNCH_PR_(FILL, SAUX, RAGGED, SRC, BLOCKS, T0, T1)                                     \
-    hipLaunchKernelGGL((rroi_bwd_pairs_relayout_kernel<FILL, SAUX, T, RAGGED>), dim3((unsigned)(pblocks + (BLOCKS))), \
-                       dim3(256), 0, stream, ws.aff, num_rois, height, width, pooled_width, NB,          \
-                       batch_size, A.lines_per_roi, A.dnb, A.dpw, KL, ws.cnt, ws.off, ws.bsum, ws.pairs,  \
-                       pblocks, SRC, ws.tdT, channels, nchunks, tt, (int)(BLOCKS), (int)(T0), (int)(T1),            \
-                       ws.scan_blocks, raw_bsum, BL, (g_tune.bwd_skip_dead ? 1 : 0) | (aggregate ? 2 : 0))
-#define RROI_LAUNCH_PR(FILL, SAUX, BLOCKS, T0, T1)                                  \
-    do {                                                                            \
-        if (ragged) RROI_LAUNCH_PR_(FILL, SAUX, true, ragged, BLOCKS, T0, T1);      \
-        else RROI_LAUNCH_PR_(FILL, SAUX, false, top_diff, BLOCKS, T0, T1);          \
-    } while (0)
-        if (buckets) {
-            // ONE launch: every pair into its pixel's bucket (or overflow chain) || the whole relayout
-            const long blocks = relayout_blocks(tiles, nchunks);
-            RROI_LAUNCH_PR(2, kBwdRelayoutAux, blocks, 0, tiles);
-        } else {
-        {
-            const long blocks = relayout_blocks(half, nchunks);
-            RROI_LAUNCH_PR(0, kBwdRelayoutAux, blocks, 0, half);
-        }
-        hipLaunchKernelGGL(rroi_scan1_kernel, dim3(ws.scan_blocks), dim3(1024), 0, stream, ws.cnt, ws.off,
-                           ws.bsum, KL.keys);
-        if (!raw_bsum) hipLaunchKernelGGL(rroi_scan2_kernel, dim3(1), dim3(1024), 0, stream, ws.bsum, ws.scan_blocks);
-        {
-            const long blocks = relayout_blocks(tiles - half, nchunks);
-            RROI_LAUNCH_PR(1, kBwdRelayoutAux, blocks, half, tiles);
-        }
-        }
-#undef RROI_LAUNCH_PR
-#undef RROI_LAUNCH_PR_
-        st = launch_status();
-        if (st != 1) return st;
-        // (3) gather: one thread group per key, no grid-stride
-        const unsigned sub_shift = P.sub_shift, tile_run = P.tile_run;
-        if (ordered) {
-            // (2b) every list in bin order: the short ones in registers, the rest queued in the counters (which the
-            // fill left at zero) for one workgroup each; then the in-order fp64 gather, in place
-            unsigned* const queue = reinterpret_cast<unsigned*>(ws.cnt);
-            hipLaunchKernelGGL(rroi_bwd_sort_lists_kernel, dim3(ceil_div((long)KL.keys, 4L)), dim3(256), 0, stream,
-                               ws.off, ws.bsum, ws.pairs, KL.keys, ws.scan_blocks, raw_bsum, queue);
-            hipLaunchKernelGGL(rroi_bwd_sort_queue_kernel, dim3(num_cus() * 4), dim3(kSortQueueThreads), 0, stream,
-                               ws.off, ws.bsum, ws.pairs, queue, ws.scan_blocks, raw_bsum);
-#define RROI_LAUNCH_OG(DSTK)                                                                                   \
-    hipLaunchKernelGGL((rroi_bwd_ordered_gather_kernel<DSTK, T>), P.grid, dim3(256), 0, stream, srcT, ws.off,   \
-                       ws.bsum, ws.pairs, bottom_diff, channels, height, width, nchunks, A.chunk_stride,          \
-                       A.line_stride, sub_shift, KL, make_fastdiv(KL.Ht * KL.Wt), make_fastdiv(KL.Wt),              \
-                       ws.scan_blocks, raw_bsum, tile_run)
-            if (P.dest == RROI_PLAN_DST_NHWC) RROI_LAUNCH_OG(kDstNhwc);
-            else RROI_LAUNCH_OG(kDstNchw);
-#undef RROI_LAUNCH_OG
-            return launch_status();
-        }
-        // the lists: count / scan / fill segments (`off` = scanned offsets) or buckets (`off` = the counters)
-        const unsigned* loff = buckets ? reinterpret_cast<const unsigned*>(ws.cnt) : ws.off;
-#define RROI_LAUNCH_G(DSTK, BUCK, DST)                                                                        \
-    hipLaunchKernelGGL((rroi_bwd_gather_kernel<DSTK, BUCK, std::remove_pointer_t<decltype(DST)>>), P.grid,    \
-                       dim3(256), 0, stream,                                                                  \
-                       srcT, loff, ws.bsum, ws.pairs, DST, channels, height, width,                           \
-                       pitch, nchunks, A.chunk_stride, A.line_stride, sub_shift, KL, make_fastdiv(KL.Ht * KL.Wt), \
-                       make_fastdiv(KL.Wt), ws.scan_blocks, raw_bsum, BL, tile_run)
-        switch (P.dest) {
-        case RROI_PLAN_DST_NHWC:   // written in place: no relayout back
-            if (buckets) RROI_LAUNCH_G(kDstNhwc, true, bottom_diff);
-            else RROI_LAUNCH_G(kDstNhwc, false, bottom_diff);
-            return launch_status();
-        case RROI_PLAN_DST_NCHW_ADD:
-            if constexpr (kF32) {   // (the launcher)
-                if (buckets) RROI_LAUNCH_G(kDstNchwAdd, true, bottom_diff);
-                else RROI_LAUNCH_G(kDstNchwAdd, false, bottom_diff);
-            }
-            return launch_status();
-        case RROI_PLAN_DST_NCHW:
-            if (buckets) RROI_LAUNCH_G(kDstNchw, true, bottom_diff);
-            else RROI_LAUNCH_G(kDstNchw, false, bottom_diff);
-            return launch_status();
-        default:
-            break;
-        }
-        if (buckets) RROI_LAUNCH_G(kDstChunkMajor, true, ws.gcm);
-        else RROI_LAUNCH_G(kDstChunkMajor, false, ws.gcm);
-#undef RROI_LAUNCH_G
-        st = launch_status();
-        if (st != 1) return st;
-    } else if constexpr (kF32) {
-        hipError_t e = hipMemsetAsync(ws.gcm, 0, (size_t)batch_size * nchunks * height * pitch * kLineBytes, stream);
-        if (e != hipSuccess) return status_of(e);
-        const int ntiles = P.ntiles;
-        const FastDiv dt = make_fastdiv((unsigned)ntiles), dp = make_fastdiv((unsigned)pooled_width);
-        if (P.vec4)
-            hipLaunchKernelGGL(rroi_bwd_tiled_kernel<true>, P.grid, dim3(kWave), 0, stream,
-                               top_diff, ws.aff, ws.gcm, num_rois, channels, height, width, pitch,
-                               pooled_width, NB, batch_size, nchunks, ntiles, dt, dp);
-        else
-            hipLaunchKernelGGL(rroi_bwd_tiled_kernel<false>, P.grid, dim3(kWave), 0, stream,
-                               top_diff, ws.aff, ws.gcm, num_rois, channels, height, width, pitch,
-                               pooled_width, NB, batch_size, nchunks, ntiles, dt, dp);
-        st = launch_status();
-        if (st != 1) return st;
-    }
-    if (accumulate) {
-        if constexpr (kF32)
-            hipLaunchKernelGGL(rroi_cm_to_nchw_kernel<true>, dim3(ptiles * nchunks * batch_size), dim3(256), 0,
-                               stream, ws.gcm, bottom_diff, channels, (int)HW, width, pitch,
-                               make_fastdiv((unsigned)width), nchunks, ptiles);
-    } else
-        hipLaunchKernelGGL((rroi_cm_to_nchw_kernel<false, T>), dim3(ptiles * nchunks * batch_size), dim3(256), 0,
-                           stream, ws.gcm, bottom_diff, channels, (int)HW, width, pitch,
-                           make_fastdiv((unsigned)width), nchunks, ptiles);
+    st = P.family == RROI_PLAN_BWD_INKERNEL ? launch_bwd_inkernel(c) : lists ? launch_bwd_lists(c) : launch_bwd_atomic(c);
+    // (a gradient written in place needs no relayout back)
+    if (st != 1 || P.dest != RROI_PLAN_DST_CHUNK_MAJOR) return st;
+    c.cm_to_nchw();
     return launch_status();
 }
 

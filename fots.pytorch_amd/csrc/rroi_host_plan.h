@@ -1,6 +1,8 @@
 // rroi_host_plan.h -- host side, part 1 of 3: what a call launches.  The tuning table, a call's Shape and its limits, the
 // grids, both workspace carvers, AUTO's rules and the dispatch (plan_forward / plan_backward / plan_forward_bucketed) with
-// its report as an rroi_align_plan.  Nothing in this file launches or touches memory; num_cus() is its only HIP call.
+// its report as an rroi_align_plan.  Every number of a launch that depends on the CU count or on the tuning table -- every
+// grid, every block count, every flag word -- is computed here, once, by the planner of the family that launches it, and
+// carried by the plan.  Nothing in this file launches or touches memory; num_cus() is its only HIP call.
 // Included by rroi_align_hip.hip inside its anonymous namespace, after the device headers.
 #pragma once
 
@@ -478,9 +480,10 @@ ForwardPlan plan_forward_gather(const Shape& S, bool out_nhwc, bool launcher_res
 }
 
 // ------------------------------------------------------------------------------------
-// The dispatch.  One function per direction decides what a call launches; the launches switch on its fields and the
-// plan query (rroi_align_forward_plan / rroi_align_backward_plan) reports them, so the two cannot disagree.  Host
-// only: no launch, no memory touched (the backward's workspace is carved at address 0 for its sizes).
+// The dispatch.  One function per direction decides what a call launches, down to every grid; the launches
+// (rroi_host_launch.h) run its fields and the plan query (rroi_align_forward_plan / rroi_align_backward_plan) reports
+// them, so the two cannot disagree.  Host only: no launch, no memory touched (the backward's workspace is carved at
+// address 0 for its sizes).
 // ------------------------------------------------------------------------------------
 bool caller_ok(int caller, bool con_idx_allowed)
 {
@@ -491,6 +494,35 @@ bool caller_ok(int caller, bool con_idx_allowed)
 inline bool dtype_ok(int dtype) { return dtype == RROI_DTYPE_FP32 || dtype == RROI_DTYPE_BF16 || dtype == RROI_DTYPE_FP16; }
 inline size_t dtype_bytes(int dtype) { return dtype == RROI_DTYPE_FP32 ? 4 : 2; }
 
+// The forward prologue launch (rroi_prologue_kernel): [relayout blocks | affine blocks | the ROI sort's block (XCD groups) |
+// the launcher's rest blocks, one per ROI].
+struct ProloguePlan {
+    int ptiles = 0;            // pixel tiles of one (image, chunk) slice
+    int relayout_tiles = 0;    // ... in all (0: channels-last features consumed in place)
+    int relayout_blocks = 0, aff_blocks = 0, sort_blocks = 0, rest_blocks = 0;
+    int grid() const { return relayout_blocks + aff_blocks + sort_blocks + rest_blocks; }
+};
+ProloguePlan plan_prologue(const Shape& S, bool zero_copy, int groups, bool launcher_rest)
+{
+    const int nchunks = S.nchunks();
+    ProloguePlan p;
+    p.ptiles = ceil_div(S.HW(), kRelayoutPx);
+    p.relayout_tiles = zero_copy ? 0 : p.ptiles * nchunks * S.batch_size;
+    // ~3 resident blocks per CU, each streaming several tiles with the next tile prefetched
+    int relayout_blocks = p.relayout_tiles;
+    if (groups > 1) relayout_blocks = (relayout_blocks + 7) / 8 * 8;   // whole XCD rounds (a block without a tile leaves)
+    if (relayout_blocks > num_cus() * g_tune.prologue_blocks_per_cu) {
+        relayout_blocks = num_cus() * g_tune.prologue_blocks_per_cu;
+        const long unit = lcm8(nchunks);   // keeps block -> chunk -> XCD stable
+        if (relayout_blocks >= unit) relayout_blocks = (int)(relayout_blocks / unit * unit);
+    }
+    p.relayout_blocks = relayout_blocks;
+    p.aff_blocks = ceil_div(S.num_rois, 256);
+    p.sort_blocks = groups > 1 ? 1 : 0;
+    p.rest_blocks = launcher_rest ? S.num_rois : 0;
+    return p;
+}
+
 struct FwdDispatch {
     int status = 0;                  // 1: the call launches this plan; 0: it refuses its arguments
     Shape shape{};                   // what the plan was made for, and what its launch runs on (the launcher's: batch 1)
@@ -500,6 +532,7 @@ struct FwdDispatch {
     bool con_idx = false;            // ... and con_idx written
     bool out_nhwc = false, zero_copy = false;
     int groups = 1;
+    ProloguePlan prologue;           // two-launch
     ForwardPlan gather{FwdKernel::kStrided, 0, 0, 0};   // fused / two-launch
     PatchPlan patch;                 // K2p
     dim3 dgrid;                      // thread-per-bin kernel; the launcher's con_idx kernel
@@ -591,6 +624,7 @@ FwdDispatch plan_forward(const Shape& shape, int feature_layout, int top_layout,
     if (feature_layout == RROI_LAYOUT_NHWC && S.channels % 4 != 0) return P;  // repack to NCHW first
     P.zero_copy = feature_layout == RROI_LAYOUT_NHWC;
     P.groups = P.launcher ? 1 : forward_groups(S.num_rois, S.nchunks());
+    P.prologue = plan_prologue(S, P.zero_copy, P.groups, P.launcher);
     const size_t map_bytes_per_xcd = P.zero_copy ? (size_t)S.batch_size * S.height * S.width * S.channels * 4 / 8
                                                  : carve(nullptr, S, feature_layout).cm_bytes / 8;
     P.gather = plan_forward_gather(S, P.out_nhwc, P.launcher, P.groups, map_bytes_per_xcd, true, dtype_bytes(dtype));
@@ -606,21 +640,34 @@ struct BwdDispatch {
     int family = RROI_PLAN_NONE;
     int trig = RROI_TRIG_DOUBLE;
     int dest = RROI_PLAN_DST_NONE;
-    bool td_nhwc = false, bd_nhwc = false, accumulate = false;
+    bool td_nhwc = false, accumulate = false;
     BwdWorkspace ws{};               // carved at address 0: sizes, key layout, bucket shift
     dim3 grid;                       // the main kernel's
-    int cslab = 0;                   // direct
-    int ntiles = 0;                  // atomic ...
-    bool vec4 = false;               // ... rroi_bwd_tiled_kernel<true> (NB % 4 == 0)
-    int nk = 0;                      // in-kernel
-    long relayout_blocks = 0;        // in-kernel: the relayout of top_diff (0: consumed in place)
-    int tt = 0;                      // top_diff relayout tiles per (roi, chunk)
-    long tiles = 0, half = 0;        // ... in all; lists: the first launch's share
-    int raw_bsum = -1;
-    int pblocks = 0;
-    bool aggregate = false;
-    unsigned sub_shift = 0, gy = 0, tile_run = 0;
-    long literal_blocks = 0;
+    int affine_blocks = 0;           // every tiled family: the affine table's launch, which also clears the lists' pixel counters
+    struct Direct {
+        int cslab = 0;
+    } direct;
+    struct Atomic {
+        int ntiles = 0;
+        bool vec4 = false;           // rroi_bwd_tiled_kernel<true> (NB % 4 == 0)
+    } atomic;
+    struct InKernel {
+        int nk = 0;
+        int tt = 0;                  // top_diff relayout tiles per (roi, chunk) ...
+        long tiles = 0;              // ... and in all
+        long relayout_blocks = 0;    // the relayout of top_diff (0: consumed in place)
+        int flags = 0;               // ... its flag word: bit 0 dead bins are not copied
+    } inkernel;
+    struct Lists {                   // LISTS, BUCKETS and ORDERED
+        int raw_bsum = -1;
+        int pblocks = 0;             // pair blocks in front of each relayout launch ...
+        int flags = 0;               // ... their flag word: bit 0 dead bins are not copied, bit 1 reservations aggregated per wave
+        int tt = 0;                  // top_diff relayout tiles per (roi, chunk) ...
+        long tiles = 0, half = 0;    // ... in all; the count launch's share
+        long count_blocks = 0, fill_blocks = 0, bucket_blocks = 0;   // relayout blocks of the count, fill and bucket launches
+        unsigned sub_shift = 0, gy = 0, tile_run = 0;
+        int sort_lists_blocks = 0, sort_queue_blocks = 0;   // ORDERED's two sort launches
+    } lists;
 };
 
 // accumulate (the reference-ABI launcher, tiled NCHW paths only): bottom_diff += gradient instead of = gradient
@@ -674,7 +721,6 @@ BwdDispatch plan_backward(const Shape& S, int top_diff_layout, int bottom_diff_l
             long blocks = (nthreads + 255) / 256;
             const long cap = (long)num_cus() * 32;
             if (blocks > cap) blocks = cap;
-            P.literal_blocks = blocks;
             P.grid = dim3((unsigned)blocks);
             return P;
         }
@@ -685,7 +731,6 @@ BwdDispatch plan_backward(const Shape& S, int top_diff_layout, int bottom_diff_l
     if (bottom_diff_layout != RROI_LAYOUT_NCHW && bottom_diff_layout != RROI_LAYOUT_NHWC) return P;
     const bool td_nhwc = top_diff_layout == RROI_LAYOUT_NHWC, bd_nhwc = bottom_diff_layout == RROI_LAYOUT_NHWC;
     P.td_nhwc = td_nhwc;
-    P.bd_nhwc = bd_nhwc;
     // channels-last tensors are read / written in place by the gather formulation only
     if ((td_nhwc || bd_nhwc) &&
         (channels % 4 != 0 || path == RROI_PATH_DIRECT || path == RROI_PATH_TILED_ATOMIC))
@@ -706,7 +751,7 @@ BwdDispatch plan_backward(const Shape& S, int top_diff_layout, int bottom_diff_l
     if (accumulate && (!tiled || bd_nhwc)) return P;
     const int nchunks = S.nchunks();
     if (!tiled) {
-        direct_grid(S, P.grid, P.cslab);
+        direct_grid(S, P.grid, P.direct.cslab);
         P.family = RROI_PLAN_BWD_DIRECT;
         P.dest = RROI_PLAN_DST_NCHW;
         P.status = 1;
@@ -753,19 +798,23 @@ BwdDispatch plan_backward(const Shape& S, int top_diff_layout, int bottom_diff_l
                          (path == RROI_PATH_TILED_BUCKETS || (ws.bucket_pref && g_tune.bwd_buckets));
     const bool lists = ragged || ordered || buckets || path == RROI_PATH_TILED_LISTS || !inkernel_ok ||
                        (path != RROI_PATH_TILED_INKERNEL && !prefer_inkernel);
-    P.tt = ceil_div(NB, kRelayoutPx);
+    const int tt = ceil_div(NB, kRelayoutPx);
+    unsigned nzero = 0;   // pixel counters that the affine launch clears
     if (gather && !lists) {
         // K3t: relayout of top_diff (one launch, masked bins skipped), then the tile gather
         P.family = RROI_PLAN_BWD_INKERNEL;
+        BwdDispatch::InKernel& K = P.inkernel;
+        K.tt = tt;
         if (!td_nhwc) {
-            P.tiles = (long)P.tt * nchunks * num_rois;
-            if (P.tiles >= (1L << 31)) return P;
-            P.relayout_blocks = relayout_blocks(P.tiles, nchunks);
+            K.tiles = (long)K.tt * nchunks * num_rois;
+            if (K.tiles >= (1L << 31)) return P;
+            K.relayout_blocks = relayout_blocks(K.tiles, nchunks);
         }
-        P.nk = nchunks > 4 ? 8 : nchunks > 2 ? 4 : nchunks > 1 ? 2 : 1;
+        K.flags = g_tune.bwd_skip_dead;
+        K.nk = nchunks > 4 ? 8 : nchunks > 2 ? 4 : nchunks > 1 ? 2 : 1;
         // 16-bit calls: at most four chunks per lane (two passes beyond 128 channels) -- the eight-chunk instantiation
         // spills to scratch (as the fp32 one does), and a 16-bit instantiation of it is not built
-        if (half && P.nk > 4) P.nk = 4;
+        if (half && K.nk > 4) K.nk = 4;
         const unsigned ntiles = ws.keys.keys / 32u;
         const unsigned per_xcd = (ntiles + 7u) / 8u;
         P.grid = dim3(per_xcd * 8u);
@@ -773,8 +822,11 @@ BwdDispatch plan_backward(const Shape& S, int top_diff_layout, int bottom_diff_l
     } else if (gather) {
         // (1) pixel -> (bin, weight) lists: count, scan, fill -- or buckets in one pass
         P.family = ordered ? RROI_PLAN_BWD_ORDERED : buckets ? RROI_PLAN_BWD_BUCKETS : RROI_PLAN_BWD_LISTS;
+        BwdDispatch::Lists& L = P.lists;
+        L.tt = tt;
+        nzero = ws.keys.keys;
         // few scan blocks: every consumer block prefix-sums their totals itself (no second scan launch)
-        P.raw_bsum = ws.scan_blocks <= kInlineScanBlocks ? 1 : 0;
+        L.raw_bsum = ws.scan_blocks <= kInlineScanBlocks ? 1 : 0;
         // one pair block per CU, looping over the bins: the pair passes need outstanding atomics,
         // not CU slots -- more blocks only take residency from the relayout (207 -> 197 us per call)
         const PatchMap dnb = make_patch_map(S.pooled_height, S.pooled_width);
@@ -797,17 +849,22 @@ BwdDispatch plan_backward(const Shape& S, int top_diff_layout, int bottom_diff_l
             const long cap = (long)num_cus() * per_cu;
             if (pblocks > cap) pblocks = (int)cap;
         }
-        P.pblocks = pblocks;
+        L.pblocks = pblocks;
         // the bucket slots reserved per WAVE through a table in LDS (pairs_reserve_wave) -- where a wave has several
         // patches to walk; with one patch per wave the table's set-up is pure latency (R = 32, C = 64: +0.8 us)
-        P.aggregate = g_tune.bwd_pair_aggregate && (long)num_rois * (dnb.lanes_per_roi / 64) > 8L * num_cus();
+        const bool aggregate = g_tune.bwd_pair_aggregate && (long)num_rois * (dnb.lanes_per_roi / 64) > 8L * num_cus();
+        L.flags = (g_tune.bwd_skip_dead ? 1 : 0) | (aggregate ? 2 : 0);
         // count || first half of the relayout;  scan;  fill || second half.  The relayout is the
         // forward's, with R "images" of PH x PW "pixels" and the masked bins skipped:
         // top_diff (R, C, NB) -> (R, NB, nchunks * 32)
-        P.tiles = td_nhwc ? 0 : (long)P.tt * nchunks * num_rois;  // nothing to relay out
-        if (P.tiles >= (1L << 31)) return P;
+        L.tiles = td_nhwc ? 0 : (long)L.tt * nchunks * num_rois;  // nothing to relay out
+        if (L.tiles >= (1L << 31)) return P;
         const long unit = nchunks;  // a block takes all chunks of a pixel range: whole ranges per launch
-        P.half = (P.tiles / 2 + unit - 1) / unit * unit < P.tiles ? (P.tiles / 2 + unit - 1) / unit * unit : P.tiles;
+        L.half = (L.tiles / 2 + unit - 1) / unit * unit < L.tiles ? (L.tiles / 2 + unit - 1) / unit * unit : L.tiles;
+        // buckets: ONE launch, every pair into its pixel's bucket (or overflow chain) || the whole relayout
+        L.bucket_blocks = relayout_blocks(L.tiles, nchunks);
+        L.count_blocks = relayout_blocks(L.half, nchunks);
+        L.fill_blocks = relayout_blocks(L.tiles - L.half, nchunks);
         // (3) gather: one thread group per key, no grid-stride
         unsigned sub_shift = 3;  // 8 lanes = one chunk
         while ((1u << sub_shift) < 8u * (unsigned)nchunks && sub_shift < 6) ++sub_shift;
@@ -831,19 +888,29 @@ BwdDispatch plan_backward(const Shape& S, int top_diff_layout, int bottom_diff_l
         const long wg_per_tile = 32 / groups_per_block;  // 1, 2, 4 or 8
         const unsigned tile_run = nchw_direct ? (unsigned)g_tune.bwd_tile_run : 0u;
         const long gblocks = ceil_div(ceil_div((long)ws.keys.keys, 32L), 8L << tile_run) * (8L << tile_run) * wg_per_tile;
-        P.sub_shift = sub_shift;
-        P.gy = gy;
-        P.tile_run = tile_run;
+        L.sub_shift = sub_shift;
+        L.gy = gy;
+        L.tile_run = tile_run;
+        // ORDERED's sorts: four lists per workgroup in registers; the queue of long lists drained by four workgroups per CU
+        L.sort_lists_blocks = ceil_div((long)ws.keys.keys, 4L);
+        L.sort_queue_blocks = num_cus() * 4;
         P.grid = dim3((unsigned)gblocks, gy);
         P.dest = bd_nhwc ? RROI_PLAN_DST_NHWC
                          : nchw_direct ? (accumulate ? RROI_PLAN_DST_NCHW_ADD : RROI_PLAN_DST_NCHW) : RROI_PLAN_DST_CHUNK_MAJOR;
     } else {
         P.family = RROI_PLAN_BWD_ATOMIC;
-        P.ntiles = ceil_div(NB, kTileBins);
-        if ((long)num_rois * P.ntiles >= (1L << 31)) return P;
-        P.grid = dim3(tiled_grid((long)num_rois * P.ntiles, nchunks));
-        P.vec4 = NB % 4 == 0;
+        P.atomic.ntiles = ceil_div(NB, kTileBins);
+        if ((long)num_rois * P.atomic.ntiles >= (1L << 31)) return P;
+        P.grid = dim3(tiled_grid((long)num_rois * P.atomic.ntiles, nchunks));
+        P.atomic.vec4 = NB % 4 == 0;
         P.dest = RROI_PLAN_DST_CHUNK_MAJOR;
+    }
+    {
+        // affine table; the list passes' pixel counters (K3g) are cleared by the same launch
+        int ablocks = ceil_div(num_rois, 256);
+        const int zblocks = nzero ? (int)std::min<long>(ceil_div((long)nzero, 1024), 2L * num_cus()) : 0;
+        if (zblocks > ablocks) ablocks = zblocks;
+        P.affine_blocks = ablocks;
     }
     P.status = 1;
     return P;
@@ -891,6 +958,7 @@ FwdDispatch plan_forward_bucketed(const Shape& S, int dtype, long long sum_poole
     // reported as RROI_PLAN_KERNEL_STRIDED_RAGGED, one XCD group
     P.gather = {FwdKernel::kStridedRagged, tiled_grid(items, S.nchunks(), g_tune.split_wgs_per_cu), ntiles, g_tune.fwd_dbg & ~0xe0};
     P.groups = 1;
+    P.prologue = plan_prologue(S, false, P.groups, false);   // (the dense prologue, unchanged: one group, no launcher)
     P.family = RROI_PLAN_FWD_TWO_LAUNCH;
     P.status = 1;
     return P;
@@ -936,17 +1004,26 @@ rroi_align_plan to_plan(const BwdDispatch& P)
     out.family = P.family;
     out.kernel = -1;
     out.groups = 0;
-    out.ntiles = P.family == RROI_PLAN_BWD_ATOMIC ? P.ntiles : 0;
+    out.ntiles = P.family == RROI_PLAN_BWD_ATOMIC ? P.atomic.ntiles : 0;
     out.grid_x = none ? 0 : (int)P.grid.x;
     out.grid_y = none ? 0 : (int)P.grid.y;
     out.zero_copy = P.td_nhwc && !none;
     out.con_idx = false;
-    out.nk = P.nk;
+    out.nk = P.inkernel.nk;
     out.kshift = P.family == RROI_PLAN_BWD_BUCKETS ? (int)P.ws.kshift : 0;
-    out.raw_bsum = lists ? P.raw_bsum : -1;
-    out.gy = lists ? (int)P.gy : 0;
+    out.raw_bsum = lists ? P.lists.raw_bsum : -1;
+    out.gy = lists ? (int)P.lists.gy : 0;
     out.dest = P.dest;
     out.accumulate = P.accumulate && !none;
-    out.vec4 = P.vec4;
+    out.vec4 = P.atomic.vec4;
     return out;
+}
+
+// A plan query's answer: 0 where the call would refuse its arguments (or `plan` is NULL), else 1 and the report.
+template <class Dispatch>
+int report_plan(const Dispatch& P, rroi_align_plan* plan)
+{
+    if (!plan || !P.status) return 0;
+    *plan = to_plan(P);
+    return 1;
 }
