@@ -87,6 +87,7 @@ CASES = [
     Case("b_inkernel_zero_copy", "bwd", 1, 64, 64, 96, 24, 8, 64, fl=NHWC, path=INKERNEL),
     Case("b_lists_nchw", "bwd", 1, 64, 64, 96, 24, 8, 64, path=LISTS),
     Case("b_lists_scan2", "bwd", 2, 32, 360, 400, 40, 8, 64, path=LISTS),
+    Case("b_lists_scan2_carry", "bwd", 2, 4, 1456, 1448, 8, 8, 32, gen="corners", path=LISTS),
     Case("b_lists_chunk_major", "bwd", 1, 160, 24, 32, 100, 8, 32, path=LISTS),
     Case("b_lists_nhwc", "bwd", 1, 64, 64, 96, 24, 11, 83, tl=NHWC, path=LISTS),
     Case("b_buckets_nchw", "bwd", 1, 64, 120, 160, 64, 11, 83),
@@ -278,7 +279,36 @@ def inputs(case, seed=0):
         r = np.stack([rng.integers(0, B, R), rng.uniform(-10, img_w + 10, R), rng.uniform(-10, img_h + 10, R), h,
                       h * rng.uniform(1, 9, R), rng.uniform(-90, 90, R)], 1).astype(np.float32)
         return f, r
+    if case.gen == "corners":     # both ends of the key space: the first rows of image 0, the last rows of image B - 1
+        h = rng.uniform(16, 48, R)
+        r = np.stack([rng.integers(0, B, R), rng.uniform(0.2, 0.8, R) * img_w, rng.uniform(0, img_h, R), h,
+                      h * rng.uniform(2, 6, R), rng.uniform(-30, 30, R)], 1).astype(np.float32)
+        r[0:2, 0], r[0:2, 2] = B - 1, img_h - rng.uniform(0, 10, 2)      # centred within 10 image pixels of the bottom edge
+        r[2:4, 0], r[2:4, 2] = 0, rng.uniform(8, 40, 2)
+        return f, r
     h = rng.uniform(4, min(64.0, img_h), R)
     r = np.stack([rng.integers(0, B, R), rng.uniform(0, img_w, R), rng.uniform(0, img_h, R), h,
                   h * rng.uniform(1, 8, R), rng.uniform(-90, 90, R)], 1).astype(np.float32)
     return f, r
+
+
+# ---- the regime of b_lists_scan2_carry: rroi_scan2_kernel scans the totals of the level-1 scan blocks (SCAN_BLOCK keys
+# each) SCAN2_ROUND at a time and carries the running sum from one round to the next
+SCAN_BLOCK, SCAN2_ROUND = 4096, 1024
+
+
+def key_count(case):
+    """Keys of the backward's pixel lists: 32 per key tile of 4 rows x 8 columns, the tiles of every image."""
+    return case.B * -(-case.H // 4) * -(-case.W // 8) * 32
+
+
+def assert_scan2_carries(case, plan, n):
+    """The case's level-2 scan runs a second round, and lists lie on both sides of it.  plan: the library's; n: the
+    oracle's term count per gradient element (backward_bound_c), (B, C, H, W)."""
+    assert plan.raw_bsum == 0, plan
+    assert key_count(case) >= SCAN2_ROUND * SCAN_BLOCK + 1, key_count(case)
+    # the keys past the first round are the last tile rows of the last image: ceil(keys / 32 / tiles per row) of them
+    over = key_count(case) - SCAN2_ROUND * SCAN_BLOCK
+    assert over >= 32 * -(-case.W // 8) * 2, "fewer than two tile rows (8 map rows) lie in the second round"
+    assert (n[case.B - 1, :, -8:] > 0).any(), "no gradient in the last 8 rows of the last image"
+    assert (n[0, :, :24] > 0).any(), "no gradient in the first rows of image 0: the carry would be 0"

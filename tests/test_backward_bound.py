@@ -81,3 +81,24 @@ def test_bound_catches_one_dropped_term(oracle):
             Wk.check_backward_elementwise(got, want, S, n, what="one term dropped")
         return
     pytest.fail("no pixel with a single droppable term")
+
+
+def test_tiny_maps_get_no_gradient_on_their_border(oracle):
+    """The border tests of the backward (kernel.cu:267-274) reject every tap on row 0, row H - 1, column 0 and column
+    W - 1: a map with H <= 2 or W <= 2 gets no gradient at all, a 3 x 3 map on pixel (1, 1) only -- what
+    test_backward_tiny_maps_every_path (tests/test_gpu_parity.py) holds every backward path to."""
+    rng = np.random.default_rng(78)
+    some = 0
+    for (H, W) in Wk.TINY_MAPS:
+        shape = (2, 3, H, W)
+        r = Wk.tiny_map_rois(rng, H, W)
+        for (ph, pw) in Wk.TINY_POOLED:
+            gout = rng.standard_normal((len(r), 3, ph, pw), dtype=np.float32)
+            want = oracle.backward_c(gout, r, shape, 1.0)
+            _, n = oracle.backward_bound_c(gout, r, shape, 1.0)
+            inner = np.zeros(shape, bool)
+            inner[:, :, 1:-1, 1:-1] = True
+            assert not n[~inner].any() and not want[~inner].any(), (H, W, ph, pw)
+            assert (H > 2 and W > 2) or not n.any()
+            some += int((n > 0).sum())
+    assert some > 0

@@ -163,6 +163,23 @@ def test_decode_beyond_262144_pixels_in_both_launch_forms(ext, dev, dtype):
 
 
 @pytest.mark.parametrize("dtype", HALF, ids=ids)
+def test_decode_of_more_than_1024_slabs_in_both_launch_forms(ext, dev, dtype):
+    """1030 x 1024 pixels = 1030 slabs (the map of test_nms.py's ordered-decode case, rounded to 16 bits): in the
+    two-launch form the workgroups of slabs 1025 .. 1029 sum the counts of the slabs before theirs in two trips.  The
+    full capacity takes that form, h * w and 1000 records the one-launch form; the count is the same in all three."""
+    from test_nms import many_workgroup_maps, passing_on_both_sides_of_slab_1024
+    h, w = 1030, 1024
+    _, segm, geo, ang = many_workgroup_maps(h, w)
+    maps = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev).to(dtype) for a in (segm, geo.transpose(2, 0, 1), ang))
+    mask = (maps[0].float() > 0.5).cpu().numpy()
+    assert passing_on_both_sides_of_slab_1024(mask)
+    full = _full_capacity(h, w)
+    assert full > h * w
+    n = _check_against_fp32(ext, maps, caps=(full, h * w, 1000))
+    assert n == int(mask.sum()) and 0.03 * h * w < n < 0.05 * h * w
+
+
+@pytest.mark.parametrize("dtype", HALF, ids=ids)
 def test_decode_special_scores_and_tiny_maps(ext, dev, dtype):
     """NaN and a score exactly equal to the threshold do not pass, +inf does, -inf does not: decided on the widened value."""
     from rroi_align.nms import CANDIDATE, decode

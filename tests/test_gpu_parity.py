@@ -178,6 +178,111 @@ def test_forward_tiny_maps_every_path(ext, oracle):
                     assert n == 0, f"{H}x{W} C={C} {ph}x{pw} path {p}: {n} elements differ, max |d| = {d}"
 
 
+@pytest.mark.parametrize("C", [1, 3, 4, 33])
+def test_backward_tiny_maps_every_path(ext, oracle, C):
+    """The backward twin of the test above: maps of one to nine pixels a side -- fewer rows than a key tile (4 x 8 pixels)
+    has, a row pitch of one, NCHW rows that are no whole 16-byte vector, lists of one pixel -- on EVERY backward path, in
+    the deterministic form, with channels-last gradients (C = 4), through the reference-ABI pair adding into a non-zero
+    bottom_diff, and in bfloat16 / float16.  The border tests (kernel.cu:267-274) reject every tap on the first and last
+    row and column: a map with H <= 2 or W <= 2 gets no gradient at all, whatever the ROIs.
+    grad_output holds multiples of 1/16 below 16 -- exact in float32, bfloat16 and float16, so one oracle run serves
+    every leg."""
+    from test_gpu_deterministic import same
+    from test_gpu_half import check_half_backward
+    rng = np.random.default_rng(78)
+    paths = (ext.PATH_DIRECT, ext.PATH_TILED, ext.PATH_TILED_LISTS, ext.PATH_TILED_BUCKETS, ext.PATH_TILED_INKERNEL,
+             ext.PATH_TILED_ATOMIC, ext.PATH_AUTO)
+    half_paths = (ext.PATH_AUTO,) + ext.GATHER_PATHS
+    some = False
+    for (H, W) in Wk.TINY_MAPS:
+        shape = (2, C, H, W)
+        R = 12
+        r = Wk.tiny_map_rois(rng, H, W, R)
+        Rr = dev(r)
+        dead = H <= 2 or W <= 2
+        for (ph, pw) in Wk.TINY_POOLED:
+            what = f"{H}x{W} C={C} {ph}x{pw}"
+            gout = (np.clip(np.round(rng.standard_normal((R, C, ph, pw)) * 16), -255, 255) / 16).astype(np.float32)
+            want = oracle.backward_c(gout, r, shape, 1.0)
+            S, n = oracle.backward_bound_c(gout, r, shape, 1.0)
+            if dead:
+                assert not n.any() and not want.any()
+            else:
+                assert not n[:, :, 0].any() and not n[:, :, -1].any() and not n[..., 0].any() and not n[..., -1].any()
+                some = some or bool(n.any())
+            G = dev(gout)
+            for p in paths:
+                got = ext.backward(G, Rr, shape, 1.0, path=p).cpu().numpy()
+                Wk.check_backward_elementwise(got, want, S, n, what=f"{what} path {p}")
+                assert not (dead and got.any()), f"{what} path {p}"
+            got = ext.backward(G, Rr, shape, 1.0, deterministic=True).cpu().numpy()
+            assert same(got, want) and not (dead and got.any()), f"{what} deterministic"
+            if C % 4 == 0:
+                Gc = G.contiguous(memory_format=torch.channels_last)
+                for p in half_paths:
+                    for Gx, cl in ((Gc, False), (G, True), (Gc, True)):
+                        got = ext.backward(Gx, Rr, shape, 1.0, path=p, channels_last_grad=cl)
+                        assert got.is_contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format)
+                        got = got.cpu().numpy()
+                        Wk.check_backward_elementwise(got, want, S, n, what=f"{what} path {p} channels-last {Gx is Gc, cl}")
+                        assert not (dead and got.any()), f"{what} path {p} channels-last"
+                got = ext.backward(Gc, Rr, shape, 1.0, channels_last_grad=True, deterministic=True).cpu().numpy()
+                assert same(got, want), f"{what} deterministic channels-last"
+            # the reference-ABI pair: con_idx from the launcher's own forward, the backward ADDS to bottom_diff
+            F = dev(rng.standard_normal(shape, dtype=np.float32))
+            out, ix, iy = (torch.empty((R, C, ph, pw), device="cuda") for _ in range(3))
+            assert ext.rroi_align_forward_cuda(ph, pw, 1.0, F, Rr, out, ix, iy) == 1
+            base = rng.standard_normal(shape, dtype=np.float32)
+            gin = dev(base)
+            assert ext.rroi_align_backward_cuda(ph, pw, 1.0, G, Rr, gin, ix, iy) == 1
+            got = gin.cpu().numpy()
+            Wk.check_backward_elementwise(got, base.astype(np.float64) + want, S, n, extra=base, what=f"{what} launcher")
+            assert not dead or np.array_equal(got, base), f"{what} launcher"
+            for dtype in (torch.bfloat16, torch.float16):
+                Gh = G.to(dtype)
+                assert torch.equal(Gh.float(), G)
+                for p in half_paths:
+                    got = ext.backward(Gh, Rr, shape, 1.0, path=p)
+                    assert got.dtype == dtype
+                    check_half_backward(got, want, S, n, dtype, f"{what} path {p} {dtype}")
+                    assert not (dead and got.float().any()), f"{what} path {p} {dtype}"
+    assert some, "no map of the list received any gradient"
+
+
+def test_backward_sparse_rois_fill_the_reservation_table(ext, oracle):
+    """The one-pass bucket build reserves its slots per WAVE where a wave has several patches of 64 bins to walk
+    (pairs_reserve_wave: more than eight patches per CU): a table of 16 key tiles in LDS, and a pair whose tile finds no
+    room in it takes its slot alone.  520 large ROIs pooled 16 x 16 on one 160 x 160 map (workloads.sparse_rois): every
+    bin in a key tile of its own, 53 .. 99 tiles per patch -- the table is full in every patch and most pairs take the
+    lone arm.  AUTO and BUCKETS, NCHW and channels-last grad_output; the same ROIs cut to 8, which do not aggregate,
+    as the contrasting leg.  Prints, per leg, the largest error as a fraction of its bound (measured on the MI355X: 0.22
+    with the table full, 0.19 without aggregation; 0.26 over the dispatch table and the fuzz)."""
+    B, C, H, W, ph, pw, s = 1, 8, 160, 160, 16, 16, 0.25
+    shape = (B, C, H, W)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    r_all = Wk.sparse_rois(520)
+    g_all = np.random.default_rng(3).standard_normal((520, C, ph, pw)).astype(np.float32)
+    for R, paths in ((520, (ext.PATH_AUTO, ext.PATH_TILED_BUCKETS)), (8, (ext.PATH_TILED_BUCKETS,))):
+        r, gout = r_all[:R], g_all[:R]
+        pr, pc, per_roi = Wk.patch_shape(ph, pw)
+        assert (R * -(-ph // pr) * -(-pw // (64 // pr)) > 8 * cus) == (R == 520) == Wk.pairs_aggregate(R, ph, pw, cus), (R, cus)
+        tiles = Wk.patch_tile_counts(oracle, shape, r, ph, pw, s)
+        assert tiles.min() > 16, (R, int(tiles.min()))
+        want = oracle.backward_c(gout, r, shape, s, threads=8)
+        S, n = oracle.backward_bound_c(gout, r, shape, s, threads=8)
+        G, Rr = dev(gout), dev(r)
+        worst = 0.0
+        for p in paths:
+            for cl in (False, True):
+                plan = ext.backward_plan(B, C, H, W, R, ph, pw, top_diff_layout=int(cl), path=p)
+                assert plan.family == ext.PLAN_BWD_BUCKETS, (R, p, cl, plan)
+                Gx = G.contiguous(memory_format=torch.channels_last) if cl else G
+                got = ext.backward(Gx, Rr, shape, s, path=p).cpu().numpy()
+                worst = max(worst, Wk.check_backward_elementwise(got, want, S, n, what=f"sparse R={R} path {p} channels-last {cl}"))
+        print(f"[sparse rois] R = {R} ({'aggregated' if R == 520 else 'one atomic per pair'}), {int(tiles.min())} .. "
+              f"{int(tiles.max())} key tiles per patch: worst element at {worst:.3f} of its bound")
+
+
 @pytest.mark.parametrize("path", ["direct", "tiled", "fused"])
 def test_forward_edge_and_degenerate_rois(ext, oracle, path):
     rng = np.random.default_rng(1)

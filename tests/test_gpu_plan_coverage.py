@@ -93,6 +93,8 @@ def run_backward(ext, oracle, case, plan):
     if case.name == "b_buckets_chains":   # some pixel's list is longer than its bucket: the overflow chains are walked
         longest = int(distinct_bins_per_pixel(oracle, f.shape, r, ph, pw).max())
         assert longest > (1 << plan.kshift), (longest, plan.kshift)
+    if case.name == "b_lists_scan2_carry":   # more than 1024 scan blocks, lists on both sides of the second round
+        PC.assert_scan2_carries(case, plan, n)
     G, Rr = dev(gout), dev(r)
     if case.caller == PC.NATIVE:
         if case.fl == PC.NHWC:

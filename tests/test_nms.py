@@ -174,19 +174,47 @@ def test_device_decode_and_get_boxes(case):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", [(40, 70), (176, 320), (600, 610)])
-def test_device_decode_is_ordered_over_many_workgroups(shape):
-    """Round 3: the decode runs one workgroup per 1024 pixels (round 2: one workgroup for the whole map);
-    the records still come out in raster order -- the merge depends on it -- also on a map large enough
-    (> 262144 pixels) for the two-launch path with per-slab counts."""
-    import torch
-    from rroi_align import nms as N
-    h, w = shape
+def many_workgroup_maps(h, w):
+    """Seeded detector maps of test_device_decode_is_ordered_over_many_workgroups: ~4 % of the pixels pass 0.5."""
     rng = np.random.default_rng(h * 1000 + w)
-    segm = (rng.random((h, w)) * 0.52).astype(np.float32)        # ~4 % of the pixels pass
+    segm = (rng.random((h, w)) * 0.52).astype(np.float32)
     geo = rng.uniform(0, 12, (h, w, 4)).astype(np.float32)
     a = rng.uniform(-1.5, 1.5, (h, w))
     ang = np.stack([np.sin(a), np.cos(a)]).astype(np.float32)
+    return rng, segm, geo, ang
+
+
+def passing_on_both_sides_of_slab_1024(mask):
+    """A slab is 1024 pixels in raster order and one workgroup; workgroup i sums slab_counts[0 .. i) 1024 at a time, so
+    the workgroups of slabs 1025 and above take a second trip.  True if pixels pass in slabs 0 .. 1023 AND in 1025 ..."""
+    flat = np.asarray(mask).reshape(-1)
+    return bool(flat[:1024 * 1024].any() and flat[1025 * 1024:].any())
+
+
+def test_the_1030_slab_map_passes_pixels_on_both_sides_of_slab_1024():
+    """CPU: the regime of the (1030, 1024) decode case below, without a GPU."""
+    h, w = 1030, 1024
+    _, segm, _, _ = many_workgroup_maps(h, w)
+    assert (h * w + 1023) // 1024 == 1030
+    mask = segm > 0.5
+    assert passing_on_both_sides_of_slab_1024(mask)
+    assert 0.03 < mask.mean() < 0.05
+    assert not passing_on_both_sides_of_slab_1024(many_workgroup_maps(600, 610)[1] > 0.5)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(40, 70), (176, 320), (600, 610), (1030, 1024)])
+def test_device_decode_is_ordered_over_many_workgroups(shape):
+    """Round 3: the decode runs one workgroup per 1024 pixels (round 2: one workgroup for the whole map);
+    the records still come out in raster order -- the merge depends on it -- also on a map large enough
+    (> 262144 pixels) for the two-launch path with per-slab counts, and on one of 1030 slabs, where the workgroups of
+    slabs 1025 .. 1029 take a second trip through the loop that sums the counts of the slabs before theirs."""
+    import torch
+    from rroi_align import nms as N
+    h, w = shape
+    rng, segm, geo, ang = many_workgroup_maps(h, w)              # ~4 % of the pixels pass
+    if h * w > 1025 * 1024:
+        assert passing_on_both_sides_of_slab_1024(segm > 0.5)
     dev = torch.device("cuda", 0)
     S, G, A = torch.from_numpy(segm).to(dev), torch.from_numpy(geo.transpose(2, 0, 1).copy()).to(dev), torch.from_numpy(ang).to(dev)
     rec, cnt = N.decode(S, G, A, 0.5)

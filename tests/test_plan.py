@@ -83,6 +83,48 @@ def test_plan_table_covers_required(ext):
     assert not extra, f"plans the table runs that REQUIRED does not list: {sorted(extra)} ({[got[k] for k in extra]})"
 
 
+def test_scan2_carry_row_is_in_its_regime(ext, oracle):
+    """b_lists_scan2_carry: more than 1024 level-1 scan blocks (rroi_scan2_kernel's second round, the carry between
+    rounds), under LISTS and under ORDERED, with lists in the first rows of image 0 and the last rows of image B - 1."""
+    import numpy as np
+    case = next(c for c in PC.CASES if c.name == "b_lists_scan2_carry")
+    plan = PC.plan_of(ext, case)
+    assert PC.key("bwd", plan, case.caller) == Bk("lists", "nchw", scan="scan2")
+    assert PC.key_count(case) == 4216576 and -(-PC.key_count(case) // PC.SCAN_BLOCK) == 1030
+    ordered = ext.backward_plan(case.B, case.C, case.H, case.W, case.R, case.ph, case.pw, deterministic=True)
+    assert ordered.family == ext.PLAN_BWD_ORDERED and ordered.raw_bsum == 0
+    f, r = PC.inputs(case)
+    gout = np.ones((case.R, case.C, case.ph, case.pw), np.float32)
+    _, n = oracle.backward_bound_c(gout, r, f.shape, PC.SCALE, threads=8)
+    PC.assert_scan2_carries(case, plan, n)
+    below = PC.Case("below", "bwd", 2, 4, 1448, 1448, 8, 8, 32, gen="corners", path=PC.LISTS)
+    assert PC.key_count(below) < PC.SCAN2_ROUND * PC.SCAN_BLOCK + 1       # (the nearest smaller map does not get there)
+
+
+MI355X_CUS = 256    # compute units of the GPU the suite runs on; the aggregation threshold is eight patches per CU
+
+
+def test_sparse_rois_are_in_the_full_table_regime(ext, oracle):
+    """The problem of test_backward_sparse_rois_fill_the_reservation_table (tests/test_gpu_parity.py): the bucket family,
+    enough patches for the per-wave reservations, and every patch on more key tiles than the wave's table has entries;
+    its first 8 ROIs are as sparse but too few to aggregate."""
+    import workloads as Wk
+    B, C, H, W, ph, pw = 1, 8, 160, 160, 16, 16
+    r = Wk.sparse_rois(520)
+    assert Wk.patch_shape(ph, pw) == (8, 8, 4)
+    for R in (520, 8):
+        for path in ((PC.AUTO, PC.BUCKETS) if R == 520 else (PC.BUCKETS,)):
+            for td in (PC.NCHW, PC.NHWC):
+                plan = ext.backward_plan(B, C, H, W, R, ph, pw, top_diff_layout=td, path=path)
+                assert plan.family == ext.PLAN_BWD_BUCKETS, (R, path, td, plan)
+        assert Wk.pairs_aggregate(R, ph, pw, MI355X_CUS) == (R == 520)
+        tiles = Wk.patch_tile_counts(oracle, (B, C, H, W), r[:R], ph, pw, PC.SCALE)
+        assert len(tiles) == 4 * R and tiles.min() > 16, (R, int(tiles.min()), int(tiles.max()))
+    # the densely pooled reference shapes stay within a dozen tiles or so: the regime is not reached by accident
+    f, rb = Wk.bench_inputs(R=64, C=1)
+    assert Wk.patch_tile_counts(oracle, (1, 1, 160, 160), rb, 8, 64, 0.25).max() <= 16
+
+
 def test_every_reachable_plan_is_required(ext):
     """A sweep of shapes, layouts, paths and callers around the thresholds: every plan key the dispatch reaches is
     REQUIRED (so a case of the table runs it) or NOT_RUN with a reason -- a combination no case runs fails here."""

@@ -112,6 +112,147 @@ def test_device_roi_builders_match_the_references_own_output():
             assert math.ceil(11 * float(ratio.item())) == int(z["m1_pw_%s_j%d" % (tag, j)])
 
 
+def same_bits(got, want):
+    """fp32 arrays equal bit for bit (-0.0 is not 0.0), NaN for NaN."""
+    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
+    nan = np.isnan(got) & np.isnan(want)
+    return got.shape == want.shape and bool(((got.view(np.uint32) == want.view(np.uint32)) | nan).all())
+
+
+def gt_boxes(n, seed):
+    """n ground-truth quads with batch indices and the reference's integer height jitter, and their rows."""
+    q = random_quads(n, seed=seed)
+    bidx = (np.arange(n) % 3).astype(np.float32)
+    jit = np.random.default_rng(seed).integers(-2, 3, n).astype(np.float32)
+    return q, bidx, jit, RB.rois_from_quads(q, bidx, mode=1, jitter=jit)[0]
+
+
+def with_box_at(q, bidx, jit, rows, pos, quad):
+    """The same batch with `quad` (no jitter) at index pos -> (quads, jitter, rows)."""
+    q, jit, rows = q.copy(), jit.copy(), rows.copy()
+    q[pos], jit[pos] = quad, 0.0
+    rows[pos] = RB.rois_from_quads(q[pos:pos + 1], bidx[pos:pos + 1], mode=1)[0][0]
+    return q, jit, rows
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [255, 256, 257, 1000])
+def test_gt_quads_to_rois_beyond_one_trip_of_the_block(n):
+    """rroi_gt_quads_to_rois_kernel is ONE block of 256 threads that walks the boxes 256 at a time and reduces the
+    largest w / h over threads: batches of 255, 256, 257 and 1000 boxes (the test above feeds it 64) with the largest
+    ratio at index 0, 255, 256 and n - 1 in turn -- thread 0's first and second trip, thread 255's only one, the last
+    box.  Every row bit for bit, the ratio the fp32 maximum of the rows' w / h, the pooled width the reference's."""
+    from rroi_align._ext import rroi_align as ext
+    q0, bidx, jit0, rows0 = gt_boxes(n, seed=100 + n)
+    B = torch.from_numpy(bidx).cuda()
+    wide = np.asarray([100, 104, 100, 100, 1300, 100, 1300, 104], np.float32)     # h = 4, w = 1200: w / h = 300
+    assert float((rows0[:, 4] / rows0[:, 3]).max()) < 250
+    for pos in sorted({0, 255, 256, n - 1}):
+        if pos >= n:
+            continue
+        q, jit, want = with_box_at(q0, bidx, jit0, rows0, pos, wide)
+        rois, ratio = ext.gt_quads_to_rois(torch.from_numpy(q).cuda(), B, torch.from_numpy(jit).cuda())
+        assert same_bits(rois.cpu().numpy(), want), (n, pos)
+        assert int(np.argmax(want[:, 4] / want[:, 3])) == pos
+        assert same_bits(ratio.cpu().numpy(), (want[:, 4] / want[:, 3]).max().reshape(1)), (n, pos)
+        assert math.ceil(11 * float(ratio.item())) == RB.train_pooled_width(want) == 3300, (n, pos)
+
+
+@pytest.mark.gpu
+def test_gt_quads_to_rois_nan_ratio_wins_at_any_position():
+    """A box whose four corners coincide has w = h = 0: w / h = 0 / 0 is NaN, and NaN wins the maximum wherever the box
+    stands (src/ocr_process.py:260-262 takes torch.max) -- also at an index only the block's second or third trip reads."""
+    from rroi_align._ext import rroi_align as ext
+    n = 600
+    q0, bidx, jit0, rows0 = gt_boxes(n, seed=7)
+    B = torch.from_numpy(bidx).cuda()
+    point = np.asarray([300, 200] * 4, np.float32)
+    rois, ratio = ext.gt_quads_to_rois(torch.from_numpy(q0).cuda(), B, torch.from_numpy(jit0).cuda())
+    assert same_bits(rois.cpu().numpy(), rows0) and float(ratio.item()) == float((rows0[:, 4] / rows0[:, 3]).max())
+    for pos in (0, 255, 256, 511, 512, n - 1):
+        q, jit, want = with_box_at(q0, bidx, jit0, rows0, pos, point)
+        assert want[pos, 3] == 0 and want[pos, 4] == 0
+        with np.errstate(invalid="ignore"):
+            assert np.isnan((want[:, 4] / want[:, 3]).max())
+        rois, ratio = ext.gt_quads_to_rois(torch.from_numpy(q).cuda(), B, torch.from_numpy(jit).cuda())
+        assert same_bits(rois.cpu().numpy(), want), pos
+        assert math.isnan(float(ratio.item())), pos
+
+
+def edge_quads():
+    """Quads off the well-formed path of random_quads (corners 0..3 = bl, tl, tr, br; edge 1->2 is the width, 0->1 the
+    height), every coordinate finite and at most 1e6 in magnitude -> ((n, 8) fp32, what each one is)."""
+    z = -0.0
+    rows = [
+        # axis-aligned, the four orientations: atan2 sees exact zeros, and +-180 degrees where edge 1->2 points to -x
+        ("upright", [10, 50, 10, 30, 210, 30, 210, 50]),
+        ("quarter turn", [50, 10, 70, 10, 70, 210, 50, 210]),
+        ("upside down: atan2(+0, -200)", [210, 30, 210, 50, 10, 50, 10, 30]),
+        ("three quarter turn", [70, 210, 50, 210, 50, 10, 70, 10]),
+        ("upside down on the x axis: atan2(-0, -200)", [210, -20, 210, 0.0, 10, z, 10, -20]),
+        ("upright on the x axis: atan2(-0, +200)", [10, 20, 10, 0.0, 210, z, 210, 20]),
+        ("quarter turn on the y axis: atan2(+200, -0)", [20, 10, 0.0, 10, z, 210, 20, 210]),
+        # edges of zero length
+        ("h == 0", [10, 30, 10, 30, 210, 30, 210, 30]),
+        ("w == 0", [10, 50, 10, 30, 10, 30, 10, 50]),
+        ("a point", [33, 44, 33, 44, 33, 44, 33, 44]),
+        ("h == 0, long: t = 11 w + 11", [0, 7, 0, 7, 30000, 7, 30000, 7]),
+        # h < 1: max(1, h)
+        ("h = 0.5", [10, 30.5, 10, 30, 90, 30, 90, 30.5]),
+        ("h = 0.25, rotated", [10, 30, 10.15, 29.8, 90.15, 89.8, 90, 90]),
+        # t // 32 < 2: the floor of 64
+        ("w / h = 1", [10, 50, 10, 30, 30, 30, 30, 50]),
+        ("t = 63", [0, 11, 0, 0, 52.5, 0, 52.5, 11]),
+        ("t = 64", [0, 11, 0, 0, 53, 0, 53, 11]),
+        ("w < h", [100, 300, 100, 100, 140, 100, 140, 300]),
+        # centres at negative coordinates: int() truncates toward zero, floor does not
+        ("centre (-3.75, -0.5)", [-14, 5, -14, -6, 6.5, -6, 6.5, 5]),
+        ("centre (-100.25, -7.75)", [-200.5, 2, -200.5, -17.5, 0, -17.5, 0, 2]),
+        ("centre (-0.25, 0.75)", [-10, 1, -10, 0, 9, 1, 10, 1]),
+        ("far out", [-999000.5, -998000, -999000.5, -998040, -998000, -998040.25, -998000, -998000]),
+        ("far out, positive", [999000, 998000, 999000, 997960, 1000000, 997960, 1000000, 998000.5]),
+        # mode 1: the angles of edges 1->2 and 0->3 on either side of +-180 degrees
+        ("straddle, 1->2 above", [210, 50, 210, 30, 10, 31, 10, 49]),
+        ("straddle, 1->2 below", [210, 50, 210, 30, 10, 29, 10, 51]),
+        ("straddle, one edge exactly 180", [210, 50, 210, 30, 10, 30, 10, 49]),
+        ("straddle, one edge exactly -180", [210, -20, 210, 0.0, 10, z, 10, -19]),
+    ]
+    q = np.asarray([r[1] for r in rows], np.float32)
+    assert np.isfinite(q).all() and np.abs(q).max() <= 1e6
+    return q, [r[0] for r in rows]
+
+
+def test_edge_quads_reach_their_arms():
+    """CPU: the restatement takes on edge_quads() the arms the device test below is about."""
+    q, names = edge_quads()
+    r0, g0 = RB.rois_from_quads(q, mode=0)
+    r1, _ = RB.rois_from_quads(q, mode=1)
+    assert {-180.0, 180.0, 90.0, -90.0} <= set(r0[:, 5].tolist()) and (np.signbit(r0[:, 5]) & (r0[:, 5] == 0)).any()
+    assert (r0[:, 3] == 0).sum() >= 3 and (r0[:, 4] == 0).sum() >= 2 and ((r0[:, 3] > 0) & (r0[:, 3] < 1)).sum() >= 2
+    by = dict(zip(names, range(len(names))))
+    assert g0[by["t = 63"]] == 64 and g0[by["t = 64"]] == 64 and g0[by["w / h = 1"]] == 64 and g0.max() > 300000
+    assert r0[by["centre (-3.75, -0.5)"], 1:3].tolist() == [-3.0, 0.0] and r1[by["centre (-3.75, -0.5)"], 1:3].tolist() == [-3.75, -0.5]
+    assert r0[by["centre (-100.25, -7.75)"], 1:3].tolist() == [-100.0, -7.0]
+    for k in ("straddle, 1->2 above", "straddle, 1->2 below"):     # the mean of two angles near +180 and -180 is near 0
+        assert abs(r0[by[k], 5]) > 179 and abs(r1[by[k], 5]) < 1
+    assert abs(r1[by["straddle, one edge exactly 180"], 5]) < 1 and abs(r1[by["straddle, one edge exactly -180"], 5]) < 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", [0, 1])
+def test_device_roi_builder_on_edge_quads(mode):
+    """rroi_quads_to_rois_kernel on edge_quads(), with per-quad batch indices: rows and pooled widths bit for bit."""
+    from rroi_align._ext import rroi_align as ext
+    q, names = edge_quads()
+    bidx = (np.arange(len(q)) % 5).astype(np.float32)
+    want, wgw = RB.rois_from_quads(q, bidx, mode=mode)
+    got, ggw = ext.quads_to_rois(torch.from_numpy(q).cuda(), torch.from_numpy(bidx).cuda(), mode)
+    got, ggw = got.cpu().numpy(), ggw.cpu().numpy()
+    for i, name in enumerate(names):
+        assert same_bits(got[i], want[i]), (name, got[i].tolist(), want[i].tolist())
+        assert ggw[i] == wgw[i], (name, int(ggw[i]), int(wgw[i]))
+
+
 @pytest.mark.gpu
 def test_ground_truth_module_and_degenerate_jitter(oracle):
     """src/ocr_process.py:196-221, :253-267 through `GroundTruthRRoiAlign`: crops equal the oracle on

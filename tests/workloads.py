@@ -89,6 +89,18 @@ def tie_rois(img=640):
     return np.asarray(rows, np.float32)
 
 
+# maps with fewer rows or columns than a key tile of the backward (4 x 8 pixels), down to one pixel
+TINY_MAPS = ((1, 1), (1, 2), (2, 1), (2, 2), (2, 3), (3, 2), (3, 3), (1, 7), (7, 1), (3, 9), (9, 3), (5, 4), (4, 5))
+TINY_POOLED = ((2, 3), (3, 21), (8, 16))
+
+
+def tiny_map_rois(rng, H, W, R=12, batch=2):
+    """ROIs at scale 1 for an H x W map of TINY_MAPS, drawn as test_forward_tiny_maps_every_path draws them: centres from
+    one pixel outside the map to one pixel outside, extents larger than the map, any angle of +-90 degrees."""
+    return np.stack([rng.integers(0, batch, R), rng.uniform(-1, W + 1, R), rng.uniform(-1, H + 1, R), rng.uniform(0.5, 2 * H + 1, R),
+                     rng.uniform(0.5, 3 * W + 1, R), rng.uniform(-90, 90, R)], 1).astype(np.float32)
+
+
 def check_backward(got, want, what="", require_abs=True, rel=1e-4, abs_bar=1e-4):
     """The backward's bar.  BASELINE configs[2] says "autograd.Function parity <= 1e-4": asserted as a MAX-ABS bound
     wherever the data allow it (`require_abs`: cfg1 ... cfg3, the training shapes, smoke -- gradients of magnitude
@@ -154,3 +166,53 @@ def check_backward_elementwise(got, want, S, n, extra=0, what=""):
     ratio = float((err[fin] / _np.maximum(bound[fin], 1e-300)).max()) if fin.any() else 0.0
     print(f"[backward bound] {what}: worst element at {ratio:.3f} of its bound, max terms per element {int(n0.max()) if n0.size else 0}")
     return ratio
+
+
+def sparse_rois(R=520, seed=5):
+    """Large, coarsely pooled ROIs for ONE 160 x 160 map at scale 0.25 (a 640 x 640 image): h and w of 520 .. 600 image
+    pixels around the middle, any angle.  Pooled 16 x 16 their bins lie 8 .. 9 map pixels apart -- each in a key tile
+    (4 rows x 8 columns of pixels) of its own, so a patch of 8 x 8 bins touches dozens of tiles."""
+    rng = np.random.default_rng(seed)
+    return np.stack([np.zeros(R), rng.uniform(280, 360, R), rng.uniform(280, 360, R), rng.uniform(520, 600, R),
+                     rng.uniform(520, 600, R), rng.uniform(-180, 180, R)], 1).astype(np.float32)
+
+
+def patch_shape(ph, pw):
+    """The backward's pair pass walks a ROI's bins in patches of 64, one per wave: (rows, columns, patches per ROI);
+    rows = the largest power of two <= min(ph, 8)."""
+    pr = 1
+    while pr * 2 <= min(ph, 8):
+        pr *= 2
+    pc = 64 // pr
+    return pr, pc, -(-ph // pr) * -(-pw // pc)
+
+
+def pairs_aggregate(R, ph, pw, cus):
+    """Whether the one-pass bucket build reserves its slots per wave through the 16-tile LDS table (more than eight
+    patches per CU) or with one atomic per pair."""
+    return R * patch_shape(ph, pw)[2] > 8 * cus
+
+
+def patch_tile_counts(oracle, shape, r, ph, pw, scale):
+    """Per patch (ROI-major, then patch row, then patch column): the number of DISTINCT key tiles -- (image, y // 4,
+    x // 8) -- its bins touch through taps that pass the backward's border tests (kernel.cu:267-274).  More than 16 and
+    the wave's reservation table is full: the pairs of the tiles it has no room for reserve their slot alone."""
+    B, _, H, W = shape
+    _, geom = oracle.forward_c(np.zeros((B, 1, H, W), np.float32), r, ph, pw, scale, return_geom=True)
+    cx, cy = geom[..., 0].reshape(-1).astype(np.float64), geom[..., 1].reshape(-1).astype(np.float64)
+    x0, x1, y0, y1 = np.floor(cx), np.ceil(cx), np.floor(cy), np.ceil(cy)   # masked bins: (0, 0), which fails every test
+    pr, pc, per_roi = patch_shape(ph, pw)
+    npx = -(-pw // pc)
+    n, iy, ix = np.unravel_index(np.arange(cx.size), (len(r), ph, pw))
+    patch = (n * per_roi + (iy // pr) * npx + ix // pc).astype(np.int64)
+    img = np.repeat(r[:, 0].astype(np.int64), ph * pw)
+    Ht, Wt = -(-H // 4), -(-W // 8)
+    taps = []
+    for yy, xx, ok in ((y0, x0, (y0 > 0) & (x0 > 0) & (y0 < H - 1) & (x0 < W - 1)),
+                       (y0, x1, (y0 > 0) & (x1 < W - 1) & (y0 < H - 1) & (x1 > 0)),
+                       (y1, x1, (y1 < H - 1) & (x1 < W - 1) & (y1 > 0) & (x1 > 0)),
+                       (y1, x0, (y1 < H - 1) & (x0 > 0) & (y1 > 0) & (x0 < W - 1))):
+        tile = (img * Ht + yy.astype(np.int64) // 4) * Wt + xx.astype(np.int64) // 8
+        taps.append(np.stack([patch[ok], tile[ok]], 1))
+    pairs = np.unique(np.concatenate(taps), axis=0)
+    return np.bincount(pairs[:, 0], minlength=len(r) * per_roi)
