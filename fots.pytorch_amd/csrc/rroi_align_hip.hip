@@ -26,7 +26,8 @@
 // in parts that are included below, inside the anonymous namespace.  Device code: rroi_device_common.h (constants,
 // geometry recipe, descriptor helpers), rroi_forward_kernels.h, rroi_backward_kernels.h, rroi_backward_tile_kernels.h,
 // rroi_callers_kernels.h, rroi_nms_kernels.h (+ rroi_nms_host.h, host C++), rroi_depthwise_kernels.h (+ rroi_depthwise_host.h:
-// the network's depthwise 3x3 convolution).  Host side: rroi_host_plan.h (tuning table,
+// the network's depthwise 3x3 convolution), rroi_instancenorm_kernels.h (+ rroi_instancenorm_host.h: its
+// InstanceNorm2d with the activation behind it).  Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
 // launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
 #include <hip/hip_runtime.h>
@@ -56,11 +57,13 @@ namespace {
 #include "rroi_nms_kernels.h"
 #include "rroi_nms_host.h"
 #include "rroi_depthwise_kernels.h"
+#include "rroi_instancenorm_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
 #include "rroi_host_launch.h"
 #include "rroi_depthwise_host.h"
+#include "rroi_instancenorm_host.h"
 
 }  // namespace
 
@@ -540,6 +543,45 @@ int rroi_depthwise3x3_forward_hip(int dtype, const void* x, const void* weight, 
         typedef decltype(tag) T;
         return launch_depthwise3x3(static_cast<const T*>(x), static_cast<const T*>(weight), static_cast<T*>(y), batch_size,
                                    channels, height, width, stride, stream);
+    });
+}
+
+// ------------------------------------------------------------------------------------
+// InstanceNorm2d of the network with its activation (header section 6): one launch, or two and a workspace.
+// ------------------------------------------------------------------------------------
+size_t rroi_instancenorm_workspace_bytes(int batch_size, int channels, int height, int width)
+{
+    size_t bytes = 0;   // the size query has no dtype: what the largest of the three plans needs (today they are one)
+    for (const int dtype : {RROI_DTYPE_FP32, RROI_DTYPE_BF16, RROI_DTYPE_FP16})
+        bytes = std::max(bytes, plan_instancenorm(dtype, batch_size, channels, height, width, num_cus()).ws_bytes);
+    return bytes;
+}
+
+int rroi_instancenorm_plan(int dtype, int batch_size, int channels, int height, int width, rroi_instancenorm_plan_info* plan)
+{
+    const InormPlan P = plan_instancenorm(dtype, batch_size, channels, height, width, num_cus());
+    if (!P.status || !plan) return 0;
+    *plan = rroi_instancenorm_plan_info{P.form, P.form == RROI_INORM_SPLIT ? 2 : 1, (int)P.nseg, (int)P.seg, (int)P.grid,
+                                        kInThreads, dtype == RROI_DTYPE_FP32 ? 4 : 8, 0};
+    return 1;
+}
+
+int rroi_instancenorm_forward_hip(int dtype, const void* x, const void* gamma, const void* beta, void* y, int batch_size,
+                                  int channels, int height, int width, double eps, float negative_slope, void* workspace,
+                                  size_t workspace_bytes, void* stream_)
+{
+    const InormPlan P = plan_instancenorm(dtype, batch_size, channels, height, width, num_cus());
+    if (!P.status) return 0;
+    if (!x || !y || (gamma == nullptr) != (beta == nullptr)) return 0;
+    if (!std::isfinite(eps) || !(eps > 0.0) || !std::isfinite(negative_slope)) return 0;
+    if (P.ws_bytes &&
+        (!workspace_ok(workspace) || workspace_bytes < rroi_instancenorm_workspace_bytes(batch_size, channels, height, width)))
+        return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_instancenorm(P, static_cast<const T*>(x), static_cast<const T*>(gamma), static_cast<const T*>(beta),
+                                   static_cast<T*>(y), (unsigned)channels, eps, negative_slope, workspace, stream);
     });
 }
 

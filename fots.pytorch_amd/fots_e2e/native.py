@@ -1,4 +1,5 @@
-"""fots_e2e.native -- the one operator of FOTSNet that runs on the package's own kernel: its depthwise 3x3 convolutions.
+"""fots_e2e.native -- the operators of FOTSNet that run on the package's own kernels: its depthwise 3x3 convolutions and
+its InstanceNorms (with the activation behind them).
 
 The 22 depthwise convolutions of the network (`_SeparableBlock.conv_sep1[0]`, `_SeparableBlock.conv2[0]`, `_smooth(...)[0]`
 in upconv1 / upconv2; tools/models.py:70-102 of the reference) are the largest single item of the end-to-end chain's
@@ -6,9 +7,16 @@ kernel time in stock torch (profiles/half_e2e.md).  `use_native_depthwise(net)` 
 calls `rroi_align._ext.rroi_align.depthwise3x3` wherever `native_ok` holds and `nn.Conv2d.forward`
 otherwise.  Opt-in, like `net.to(torch.bfloat16)`: the caller switches the network, the pipeline takes no new argument.
 Inference only: a call that needs a gradient takes the stock path, so training is untouched.
+
+The 52 `nn.InstanceNorm2d` of the network (49 run per pass) are the next item of that trace: MIOpen's spatial batch norm
+in fp32, two ATen kernels and the casts around them in 16 bits, and a LeakyReLU / ReLU launch behind each.
+`use_native_instancenorm(net)` switches them to `NativeInstanceNorm2d`, which calls
+`rroi_align._ext.rroi_align.instance_norm` wherever `instancenorm_ok` holds, and lets a norm that is directly
+followed by its activation inside an `nn.Sequential` apply that activation itself.  The same terms: opt-in, inference only.
 """
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 _DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
@@ -62,3 +70,104 @@ def use_native_depthwise(net: nn.Module, enable: bool = True) -> int:
             m.__class__ = dst
             n += 1
     return n
+
+
+# --------------------------------------------------------------------------- InstanceNorm2d (+ activation), DESIGN 5.11
+def instancenorm_ok(m, x) -> bool:
+    """True where `m(x)` may run the native kernel: pure, no GPU needed to ask.  Instance statistics only (a module that
+    tracks running statistics keeps the stock path, in training and in eval; so does a plane of one element, which the
+    stock module refuses with a ValueError)."""
+    w = m._parameters.get("weight")
+    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype in _DTYPES and x.is_contiguous()
+            and not m.track_running_stats and x.size(1) == m.num_features and 0 < x.numel() < (1 << 31)
+            and x.size(2) * x.size(3) > 1 and not _inorm_slower(x)
+            and (w is None or (w.dtype == x.dtype and w.device == x.device and m._parameters.get("bias") is not None))
+            and not torch.is_autocast_enabled()
+            and not (torch.is_grad_enabled() and (x.requires_grad or (w is not None and (w.requires_grad
+                                                                                         or m._parameters["bias"].requires_grad)))))
+
+
+def _inorm_slower(x) -> bool:
+    """The one shape class in which the native kernel measured slower than the stock one (profiles/native_instancenorm.md):
+    float32, very many tiny planes -- 49,152 planes of 64 / 96 elements (the head's last norm on eight images' crops):
+    77-85 us against MIOpen's 30-35; a workgroup per plane is mostly idle lanes there.  6,144 such planes win (12 against
+    33 us) and so do 49,152 planes of 320 elements (93 against 157); the line between them is drawn by interpolation at
+    16,384 planes and 128 elements.  The 16-bit types win at every measured shape (98 against 346 us in this one)."""
+    return x.dtype == torch.float32 and x.size(2) * x.size(3) <= 128 and x.size(0) * x.size(1) > 16384
+
+
+class NativeInstanceNorm2d(nn.InstanceNorm2d):
+    """An `nn.InstanceNorm2d` (same parameters, same `state_dict` keys) whose forward runs the native kernel where
+    `instancenorm_ok(self, x)` holds.  `fused_slope` (None: nothing absorbed) is the negative slope of an activation that
+    `use_native_instancenorm` has folded into this module: it is applied on BOTH paths, so the pair computes the same
+    function whichever path a call takes."""
+    fused_slope = None
+
+    def forward(self, x):
+        slope = self.fused_slope
+        if instancenorm_ok(self, x):
+            p = self._parameters
+            return _ext()._instance_norm_run(x, p.get("weight"), p.get("bias"), self.eps, 1.0 if slope is None else slope)
+        y = super().forward(x)
+        return y if slope is None else F.leaky_relu(y, slope)
+
+
+class AbsorbedLeakyReLU(nn.LeakyReLU):
+    """An `nn.LeakyReLU` whose work the `NativeInstanceNorm2d` in front of it does: returns its input."""
+
+    def forward(self, x):
+        return x
+
+
+class AbsorbedReLU(nn.ReLU):
+    """An `nn.ReLU` whose work the `NativeInstanceNorm2d` in front of it does: returns its input."""
+
+    def forward(self, x):
+        return x
+
+
+_ABSORBED = {nn.LeakyReLU: AbsorbedLeakyReLU, nn.ReLU: AbsorbedReLU}
+
+
+def use_native_instancenorm(net: nn.Module, enable: bool = True, fuse_activation: bool = True):
+    """Switch every `nn.InstanceNorm2d` of `net` to `NativeInstanceNorm2d` (52 for `FOTSNet()`), and -- with
+    `fuse_activation` -- let every switched norm that an `nn.Sequential` follows directly with an `nn.LeakyReLU` /
+    `nn.ReLU` take over that activation's slope, the activation becoming a pass-through (20 pairs for `FOTSNet()`).  A pair
+    is fused only where both modules occur once in `net`: a module that is also called from somewhere else keeps its
+    meaning.  enable=False: every class back, every slope removed.  Only classes change: no parameter is copied, no key of
+    the state_dict moves.  Activations applied functionally (`F.leaky_relu` in a forward) stay what they are.
+    Returns (norms switched, activations switched)."""
+    norms = acts = 0
+    if not enable:
+        for m in net.modules():
+            if type(m) is NativeInstanceNorm2d:
+                m.__dict__.pop("fused_slope", None)
+                m.__class__ = nn.InstanceNorm2d
+                norms += 1
+            else:
+                for stock, absorbed in _ABSORBED.items():
+                    if type(m) is absorbed:
+                        m.__class__ = stock
+                        acts += 1
+        return norms, acts
+    for m in net.modules():
+        if type(m) is nn.InstanceNorm2d:
+            m.__class__ = NativeInstanceNorm2d
+            norms += 1
+    if fuse_activation:
+        uses = {}
+        for m in net.modules():
+            for child in m._modules.values():
+                if child is not None:
+                    uses[id(child)] = uses.get(id(child), 0) + 1
+        for seq in net.modules():
+            if not isinstance(seq, nn.Sequential):
+                continue
+            mods = list(seq._modules.values())
+            for norm, act in zip(mods, mods[1:]):
+                if (type(norm) is NativeInstanceNorm2d and norm.fused_slope is None and type(act) in _ABSORBED
+                        and uses[id(norm)] == 1 and uses[id(act)] == 1):
+                    norm.fused_slope = float(getattr(act, "negative_slope", 0.0))
+                    act.__class__ = _ABSORBED[type(act)]
+                    acts += 1
+    return norms, acts

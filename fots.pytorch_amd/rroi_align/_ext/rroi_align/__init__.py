@@ -143,6 +143,21 @@ PLAN_KERNEL_STRIDED_RAGGED = 5
 # the network's depthwise 3x3 convolution (header section 5; after 0.10.0, same version string: found by symbol)
 _lib.rroi_depthwise3x3_forward_hip.restype = _i
 _lib.rroi_depthwise3x3_forward_hip.argtypes = [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]
+# the network's InstanceNorm2d with its activation (header section 6; after 0.10.0, same version string: found by symbol)
+_d = ctypes.c_double
+
+
+class _InormPlan(ctypes.Structure):
+    _fields_ = [(n, _i) for n in ("form", "launches", "segments", "segment_elems", "grid_x", "block", "vector_elems", "reserved")]
+
+
+_lib.rroi_instancenorm_forward_hip.restype = _i
+_lib.rroi_instancenorm_forward_hip.argtypes = [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _f, _vp, _sz, _vp]
+_lib.rroi_instancenorm_workspace_bytes.restype = _sz
+_lib.rroi_instancenorm_workspace_bytes.argtypes = [_i] * 4
+_lib.rroi_instancenorm_plan.restype = _i
+_lib.rroi_instancenorm_plan.argtypes = [_i] * 5 + [ctypes.POINTER(_InormPlan)]
+INORM_PLANE, INORM_SPLIT = 1, 2
 
 EXPORTS = (
     "RROIAlignForwardLaucher", "RROIAlignBackwardLaucher", "rroi_align_forward_hip",
@@ -163,6 +178,7 @@ EXPORTS = (
     "rroi_align_forward_bucketed_plan", "rroi_align_backward_bucketed_plan",
     "rroi_align_forward_bucketed_workspace_bytes", "rroi_align_backward_bucketed_workspace_bytes",
     "rroi_depthwise3x3_forward_hip",
+    "rroi_instancenorm_forward_hip", "rroi_instancenorm_workspace_bytes", "rroi_instancenorm_plan",
 )
 
 # What a call launches (rroi_align_forward_plan / rroi_align_backward_plan); the fields of rroi_align_plan.
@@ -666,6 +682,83 @@ def _depthwise3x3_run(x: torch.Tensor, weight: torch.Tensor, stride: int) -> tor
                                             stride, _stream())
     if st != 1:
         _check(st, "rroi_depthwise3x3_forward_hip")
+    return out
+
+
+# --------------------------------------------------------------------------- InstanceNorm2d (header section 6)
+InstanceNormPlan = collections.namedtuple("InstanceNormPlan", [n for n, _ in _InormPlan._fields_[:-1]])
+
+
+def instance_norm_plan(batch_size, channels, height, width, dtype=DTYPE_FP32) -> InstanceNormPlan:
+    """What `instance_norm` launches for a tensor of this shape (host only, no GPU needed: 256 CUs are assumed without
+    one): the form (INORM_PLANE / INORM_SPLIT), its launches, segments per plane, elements per segment, the grid.
+    ValueError where the call would refuse the arguments."""
+    p = _InormPlan()
+    if _lib.rroi_instancenorm_plan(dtype_code(dtype), int(batch_size), int(channels), int(height), int(width),
+                                   ctypes.byref(p)) != 1:
+        raise ValueError("rroi_instancenorm_plan: the call would refuse these arguments")
+    return InstanceNormPlan(*(getattr(p, n) for n in InstanceNormPlan._fields))
+
+
+def instance_norm_workspace_bytes(batch_size, channels, height, width) -> int:
+    """Bytes of workspace `rroi_instancenorm_forward_hip` needs for this shape: 0 in the plane form."""
+    return int(_lib.rroi_instancenorm_workspace_bytes(int(batch_size), int(channels), int(height), int(width)))
+
+
+def instance_norm(x: torch.Tensor, weight=None, bias=None, eps: float = 1e-5, negative_slope: float = 1.0) -> torch.Tensor:
+    """InstanceNorm2d of (N,C,H,W) `x` over each (n, c) plane (biased variance, instance statistics), then
+    `v < 0 ? v * negative_slope : v` (1.0: no activation, 0.0: ReLU) -- DESIGN 5.11.  float32, bfloat16 or float16;
+    weight and bias are (C,) of x's dtype, or both None.  x is made NCHW-contiguous.  Statistics in double, shifted by the
+    plane's first element; one rounding to fp32 and one to the tensor's type; the same bits on every run.  Forward only (no
+    autograd).  ValueError for mismatched shapes or dtypes, RuntimeError for CPU tensors."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a torch.Tensor")
+    if x.dim() != 4:
+        raise ValueError(f"x must be (N,C,H,W), got {tuple(x.shape)}")
+    if (weight is None) != (bias is None):
+        raise ValueError("weight and bias come together, or neither")
+    C = x.size(1)
+    for name, p in (("weight", weight), ("bias", bias)):
+        if p is None:
+            continue
+        if not isinstance(p, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if tuple(p.shape) != (C,):
+            raise ValueError(f"{name} must be {(C,)} for x {tuple(x.shape)}, got {tuple(p.shape)}")
+        if p.dtype != x.dtype:
+            raise ValueError(f"x and {name} must have one dtype, got {x.dtype} and {p.dtype}")
+    _require_cuda_f32(x, "x", _IO_DTYPES)
+    for name, p in (("weight", weight), ("bias", bias)):
+        if p is not None:
+            _require_cuda_f32(p, name, _IO_DTYPES)
+            if p.device != x.device:
+                raise ValueError(f"x and {name} must be on the same device")
+    if C < 1 or x.size(2) < 1 or x.size(3) < 1:
+        raise ValueError(f"x must have at least one channel, row and column, got {tuple(x.shape)}")
+    if weight is not None:
+        weight, bias = weight.contiguous(), bias.contiguous()
+    return _instance_norm_run(x.contiguous(), weight, bias, float(eps), float(negative_slope))
+
+
+def _instance_norm_run(x: torch.Tensor, weight, bias, eps: float, negative_slope: float) -> torch.Tensor:
+    """The call itself, for arguments already checked (instance_norm above; fots_e2e.native after instancenorm_ok): x is a
+    contiguous CUDA (N,C,H,W) tensor, weight and bias contiguous (C,) of its dtype and device or both None.  Kept lean: a
+    network pass makes 49 of these calls and the one-image leg of the pipeline is bound by host time."""
+    index = x.device.index
+    if index != torch.cuda.current_device():
+        with torch.cuda.device(index):
+            return _instance_norm_run(x, weight, bias, eps, negative_slope)
+    out = torch.empty_like(x)
+    N, C, H, W = x.shape
+    if N == 0:
+        return out
+    nbytes = _lib.rroi_instancenorm_workspace_bytes(N, C, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    st = _lib.rroi_instancenorm_forward_hip(_DTYPES[x.dtype], x.data_ptr(), None if weight is None else weight.data_ptr(),
+                                            None if bias is None else bias.data_ptr(), out.data_ptr(), N, C, H, W, eps,
+                                            negative_slope, None if ws is None else ws.data_ptr(), nbytes, _stream())
+    if st != 1:
+        _check(st, "rroi_instancenorm_forward_hip")
     return out
 
 

@@ -498,6 +498,64 @@ int rroi_ctc_greedy_decode_typed_hip(int dtype, const void* logits, int num_seqs
 int rroi_depthwise3x3_forward_hip(int dtype, const void* x, const void* weight, void* y, int batch_size, int channels,
                                   int height, int width, int stride, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * 6. The network's InstanceNorm2d with the activation that follows it, replacing the stock
+ *    `nn.InstanceNorm2d(c, eps, affine)` of tools/models.py (MIOpen's spatial batch norm in fp32, two ATen kernels in
+ *    16 bits) and, optionally, the LeakyReLU / ReLU launch behind it.  Forward only, instance statistics only (never
+ *    running statistics); opt-in from Python (fots_e2e.native.use_native_instancenorm).
+ *
+ *      x      (N, C, H, W)  contiguous NCHW, element type `dtype` (RROI_DTYPE_*)
+ *      gamma, beta  (C)     the same element type, or BOTH NULL (= 1 and 0: affine=False)
+ *      y      (N, C, H, W)  the same type; every element is written and nothing else is (beyond the workspace); x and y
+ *                           must not overlap
+ *      eps                  finite, > 0
+ *      negative_slope       finite: 1.0 = no activation, 0.0 = ReLU, 0.01 = the network's LeakyReLU
+ *
+ *    Arithmetic per (n, c) plane of n = H * W elements, fixed so that two identical calls give identical bits:
+ *      every element is widened exactly to double where it is loaded;  K = the plane's first element
+ *      s1 = sum (x - K),  s2 = sum (x - K)^2      in double, in an order that depends on the argument list alone
+ *                                                 (no atomics; the order changes with the form and with x mod 16 bytes)
+ *      m = s1 / n,  mean = K + m,  var = s2 / n - m * m, negative -> 0 (a NaN stays),  a = gamma / sqrt(var + eps),
+ *      b = beta - mean * a                        all in double, each operation rounded once (no contraction)
+ *      v = (float)((double)x * a + b);  v = v < 0 ? v * negative_slope : v  (fp32);  y = (T)v
+ *    -- one plain conversion to the tensor's type (nearest even, NaN kept).  A NaN or +-inf anywhere in a plane makes
+ *    that whole plane NaN and touches no other plane; fp32 subnormals are kept on input and output.
+ *    Any element-aligned x and y work (a view one element into an allocation is a legal argument).
+ *
+ *    Two forms, chosen by the library as a pure function of (dtype, N, C, H, W, CU count) -- rroi_instancenorm_plan
+ *    reports the choice without a launch (256 CUs where there is no GPU):
+ *      RROI_INORM_PLANE  one launch, one workgroup per plane; no workspace (NULL / 0 is accepted, a buffer that is
+ *                        handed over is left alone)
+ *      RROI_INORM_SPLIT  two launches for few large planes: `segments` workgroups per plane leave one {s1, s2} pair of
+ *                        doubles each in the workspace, then every workgroup of the second launch adds its plane's pairs
+ *                        in one fixed order and maps its segment.  Needs rroi_instancenorm_workspace_bytes(N, C, H, W)
+ *                        bytes at a 256-byte-aligned address; the contents before and after the call mean nothing.
+ *    Returns 1 / 0 / -hipError.  0, before any launch: an unknown dtype, a dimension below 1, N * C * H * W >= 2^31, a
+ *    NULL x or y, exactly one of gamma / beta NULL, eps not finite or not > 0, negative_slope not finite, and -- for a
+ *    plan that needs the workspace -- a NULL workspace, one that is not a multiple of 256, or workspace_bytes below
+ *    the size query's answer.  The call only enqueues on `stream`, allocates nothing and can be captured into a HIP graph.
+ *    Arrived after 0.10.0 under the same version string: detect it by symbol.
+ * ------------------------------------------------------------------------- */
+#define RROI_INORM_PLANE 1
+#define RROI_INORM_SPLIT 2
+typedef struct rroi_instancenorm_plan_info {
+    int form;           /* RROI_INORM_PLANE / RROI_INORM_SPLIT */
+    int launches;       /* 1 / 2 */
+    int segments;       /* workgroups per plane (1 in the plane form) */
+    int segment_elems;  /* elements per segment; the last segment takes what is left (H * W in the plane form) */
+    int grid_x;         /* workgroups per launch: N * C * segments */
+    int block;          /* threads per workgroup */
+    int vector_elems;   /* elements per 16-byte access */
+    int reserved;
+} rroi_instancenorm_plan_info;
+int rroi_instancenorm_forward_hip(int dtype, const void* x, const void* gamma, const void* beta, void* y, int batch_size,
+                                  int channels, int height, int width, double eps, float negative_slope, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+/* host only; 0 where the plan needs no workspace (and for arguments the call would refuse) */
+size_t rroi_instancenorm_workspace_bytes(int batch_size, int channels, int height, int width);
+/* host only, no launch; 1, or 0 for arguments the call would refuse */
+int rroi_instancenorm_plan(int dtype, int batch_size, int channels, int height, int width, rroi_instancenorm_plan_info* plan);
+
 /* Bin centres only: geom (R, PH, PW, 2) = (bin_cx, bin_cy), 0 where the bin is
  * outside the ROI's pooled width (kernel.cu:86-107).  Diagnostic / test hook. */
 int rroi_align_bin_centres_hip(float spatial_scale, int num_rois, int height, int width,
@@ -527,8 +585,8 @@ int rroi_align_get_trig_recipe_hip(void);
 
 /* Identification: "rroi_align_hip <version> gfx950" (0.7.0: per-call trig recipe, device-wide setter removed; 0.8.0: launcher scratch reused within a capture, table of 64, stats; 0.9.0: plan query; 0.10.0: bfloat16 / float16 tensors).
  * The typed callers' entry points (rroi_rbox_decode_typed_hip, rroi_ctc_greedy_decode_typed_hip) arrived after 0.10.0 under
- * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b and the depthwise
- * convolution of section 5. */
+ * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b, the depthwise
+ * convolution of section 5 and the InstanceNorm of section 6. */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
