@@ -27,7 +27,8 @@
 // geometry recipe, descriptor helpers), rroi_forward_kernels.h, rroi_backward_kernels.h, rroi_backward_tile_kernels.h,
 // rroi_callers_kernels.h, rroi_nms_kernels.h (+ rroi_nms_host.h, host C++), rroi_depthwise_kernels.h (+ rroi_depthwise_host.h:
 // the network's depthwise 3x3 convolution), rroi_instancenorm_kernels.h (+ rroi_instancenorm_host.h: its
-// InstanceNorm2d with the activation behind it).  Host side: rroi_host_plan.h (tuning table,
+// InstanceNorm2d with the activation behind it), rroi_heads_kernels.h (+ rroi_heads_host.h: its detection heads
+// and attention gate).  Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
 // launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
 #include <hip/hip_runtime.h>
@@ -58,12 +59,14 @@ namespace {
 #include "rroi_nms_host.h"
 #include "rroi_depthwise_kernels.h"
 #include "rroi_instancenorm_kernels.h"
+#include "rroi_heads_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
 #include "rroi_host_launch.h"
 #include "rroi_depthwise_host.h"
 #include "rroi_instancenorm_host.h"
+#include "rroi_heads_host.h"
 
 }  // namespace
 
@@ -582,6 +585,77 @@ int rroi_instancenorm_forward_hip(int dtype, const void* x, const void* gamma, c
         typedef decltype(tag) T;
         return launch_instancenorm(P, static_cast<const T*>(x), static_cast<const T*>(gamma), static_cast<const T*>(beta),
                                    static_cast<T*>(y), (unsigned)channels, eps, negative_slope, workspace, stream);
+    });
+}
+
+// ------------------------------------------------------------------------------------
+// Detection heads and attention gate of the network (header section 7): one launch, no workspace.
+// ------------------------------------------------------------------------------------
+int rroi_heads_plan(int dtype, int outputs, int batch_size, int channels, int height, int width, rroi_heads_plan_info* plan)
+{
+    const HeadsPlan P = plan_heads(dtype, outputs, batch_size, channels, height, width, num_cus());
+    if (!P.status || !plan) return 0;
+    *plan = rroi_heads_plan_info{P.V, P.S, (int)P.tiles, (int)P.grid, P.S * 64, (int)P.lds_bytes, (int)P.cb, 0};
+    return 1;
+}
+
+static int heads_impl(const HeadsPlan& P, int dtype, const void* x, const void* w_score, const void* b_score,
+                      const void* w_rbox, const void* b_rbox, const void* w_angle, const void* b_angle, void* score, void* rbox,
+                      void* angle, int channels, double rbox_scale, void* stream_)
+{
+    if (!P.status) return 0;
+    if (!x || !w_score || !w_rbox || !w_angle || !score || !rbox || !angle) return 0;
+    if (!std::isfinite(rbox_scale)) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_pointwise<T, 7, kPwEpiHeads>(
+            P, static_cast<const T*>(x), static_cast<const T*>(w_score), static_cast<const T*>(b_score),
+            static_cast<const T*>(w_rbox), static_cast<const T*>(b_rbox), static_cast<const T*>(w_angle),
+            static_cast<const T*>(b_angle), static_cast<T*>(score), static_cast<T*>(rbox), static_cast<T*>(angle),
+            (unsigned)channels, rbox_scale, stream);
+    });
+}
+
+int rroi_heads_forward_hip(int dtype, const void* x, const void* w_score, const void* b_score, const void* w_rbox,
+                           const void* b_rbox, const void* w_angle, const void* b_angle, void* score, void* rbox, void* angle,
+                           int batch_size, int channels, int height, int width, double rbox_scale, void* stream)
+{
+    return heads_impl(plan_heads(dtype, 7, batch_size, channels, height, width, num_cus()), dtype, x, w_score, b_score, w_rbox,
+                      b_rbox, w_angle, b_angle, score, rbox, angle, channels, rbox_scale, stream);
+}
+
+#ifdef RROI_HEADS_MEASURE
+// Measurement build only (`make heads-forms`; not declared in the header, not in the shipped library): the heads with V
+// and S forced, for the comparison of the plan rule against its neighbours (tools/heads_bench.py --forms).
+// *v_used / *s_used report what ran after the caps of plan_heads.
+int rroi_heads_forward_forced_hip(int dtype, const void* x, const void* w_score, const void* b_score, const void* w_rbox,
+                                  const void* b_rbox, const void* w_angle, const void* b_angle, void* score, void* rbox,
+                                  void* angle, int batch_size, int channels, int height, int width, double rbox_scale,
+                                  int force_v, int force_s, int* v_used, int* s_used, void* stream)
+{
+    const HeadsPlan P = plan_heads(dtype, 7, batch_size, channels, height, width, num_cus(), force_v, force_s);
+    if (v_used) *v_used = P.V;
+    if (s_used) *s_used = P.S;
+    return heads_impl(P, dtype, x, w_score, b_score, w_rbox, b_rbox, w_angle, b_angle, score, rbox, angle, channels, rbox_scale,
+                      stream);
+}
+#endif
+
+int rroi_gate_forward_hip(int dtype, const void* x, const void* w, const void* b, void* y, int batch_size, int channels,
+                          int height, int width, void* stream_)
+{
+    const HeadsPlan P = plan_heads(dtype, 1, batch_size, channels, height, width, num_cus());
+    if (!P.status) return 0;
+    if (!x || !w || !y) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_pointwise<T, 1, kPwEpiSigmoid>(P, static_cast<const T*>(x), static_cast<const T*>(w),
+                                                     static_cast<const T*>(b), static_cast<const T*>(nullptr),
+                                                     static_cast<const T*>(nullptr), static_cast<const T*>(nullptr),
+                                                     static_cast<const T*>(nullptr), static_cast<T*>(y), static_cast<T*>(nullptr),
+                                                     static_cast<T*>(nullptr), (unsigned)channels, 1.0, stream);
     });
 }
 

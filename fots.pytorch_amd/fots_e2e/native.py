@@ -1,5 +1,5 @@
-"""fots_e2e.native -- the operators of FOTSNet that run on the package's own kernels: its depthwise 3x3 convolutions and
-its InstanceNorms (with the activation behind them).
+"""fots_e2e.native -- the operators of FOTSNet that run on the package's own kernels: its depthwise 3x3 convolutions, its
+InstanceNorms (with the activation behind them), and its detection heads and attention gates.
 
 The 22 depthwise convolutions of the network (`_SeparableBlock.conv_sep1[0]`, `_SeparableBlock.conv2[0]`, `_smooth(...)[0]`
 in upconv1 / upconv2; tools/models.py:70-102 of the reference) are the largest single item of the end-to-end chain's
@@ -13,10 +13,17 @@ in fp32, two ATen kernels and the casts around them in 16 bits, and a LeakyReLU 
 `use_native_instancenorm(net)` switches them to `NativeInstanceNorm2d`, which calls
 `rroi_align._ext.rroi_align.instance_norm` wherever `instancenorm_ok` holds, and lets a norm that is directly
 followed by its activation inside an `nn.Sequential` apply that activation itself.  The same terms: opt-in, inference only.
+
+The tail of `FOTSNet.forward` -- `_heads` twice per pass (three 1x1 convolutions that each read the 256-channel map, and
+eleven elementwise launches on maps of 1 to 4 channels) and the convolution + sigmoid of `_gate` three times -- is one
+launch per call after `use_native_heads(net)`: `rroi_align._ext.rroi_align.heads` / `gate` wherever `heads_ok`
+holds, the stock methods otherwise.  The bilinear resize behind the gate stays stock.  The same terms once more.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from .model import FOTSNet
 
 _DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
@@ -171,3 +178,62 @@ def use_native_instancenorm(net: nn.Module, enable: bool = True, fuse_activation
                     act.__class__ = _ABSORBED[type(act)]
                     acts += 1
     return norms, acts
+
+
+# --------------------------------------------------------------------------- detection heads and attention gate, DESIGN 5.12
+_HEAD_CONVS = (("act", 1), ("rbox", 4), ("angle", 2))
+_GATE_CONVS = (("conv_attenton", 1),)
+
+
+def _pointwise_conv_ok(m, outputs, t) -> bool:
+    """A plain 1x1, stride-1, ungrouped `nn.Conv2d` from t's channels to `outputs`, with t's dtype, on t's device, that
+    needs no gradient."""
+    if type(m) is not nn.Conv2d:
+        return False
+    w, b = m._parameters["weight"], m._parameters["bias"]
+    return (m.kernel_size == (1, 1) and m.stride == (1, 1) and m.padding == (0, 0) and m.dilation == (1, 1)
+            and m.groups == 1 and m.out_channels == outputs and m.in_channels == t.size(1) and m.padding_mode == "zeros"
+            and w.dtype == t.dtype and w.device == t.device and (b is None or (b.dtype == t.dtype and b.device == t.device))
+            and not (torch.is_grad_enabled() and (w.requires_grad or (b is not None and b.requires_grad))))
+
+
+def heads_ok(net, t, gate: bool = False) -> bool:
+    """True where `net._heads(t)` (gate=True: the convolution and sigmoid of `net._gate(t, like)`) may run the native
+    kernel: pure, no GPU needed to ask.  No shape class is declined for speed: every measured one won
+    (profiles/native_heads.md)."""
+    return (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 4 and t.dtype in _DTYPES and t.is_contiguous()
+            and 0 < t.numel() < (1 << 31)
+            and not torch.is_autocast_enabled()
+            and not (torch.is_grad_enabled() and t.requires_grad)
+            and all(_pointwise_conv_ok(net._modules.get(name), k, t) for name, k in (_GATE_CONVS if gate else _HEAD_CONVS)))
+
+
+def _wb(m):
+    p = m._parameters
+    return p["weight"], p["bias"]
+
+
+class NativeHeadsFOTSNet(FOTSNet):
+    """A `FOTSNet` (same modules, same `state_dict` keys) whose `_heads` and `_gate` run the native kernel where `heads_ok`
+    holds."""
+
+    def _heads(self, t):
+        if heads_ok(self, t):
+            return _ext()._heads_run(t, *_wb(self.act), *_wb(self.rbox), *_wb(self.angle), 128.0)
+        return super()._heads(t)
+
+    def _gate(self, t, like):
+        if heads_ok(self, t, gate=True):
+            return self._up(_ext()._gate_run(t, *_wb(self.conv_attenton)), like)
+        return super()._gate(t, like)
+
+
+def use_native_heads(net: nn.Module, enable: bool = True) -> bool:
+    """Switch a network whose type is exactly `FOTSNet` to `NativeHeadsFOTSNet` (enable=False: back).  Only the class of
+    the network changes: no parameter is copied, no key of the state_dict moves; the module switches above compose with it
+    in any order.  A network of any other type is left alone.  Returns whether the class was switched."""
+    src, dst = (FOTSNet, NativeHeadsFOTSNet) if enable else (NativeHeadsFOTSNet, FOTSNet)
+    if type(net) is not src:
+        return False
+    net.__class__ = dst
+    return True

@@ -556,6 +556,58 @@ size_t rroi_instancenorm_workspace_bytes(int batch_size, int channels, int heigh
 /* host only, no launch; 1, or 0 for arguments the call would refuse */
 int rroi_instancenorm_plan(int dtype, int batch_size, int channels, int height, int width, rroi_instancenorm_plan_info* plan);
 
+/* ------------------------------------------------------------------------- *
+ * 7. The network's detection heads and attention gate: a 1x1 convolution with bias from many channels to
+ *    7 outputs (heads: `act` 1, `rbox` 4, `angle` 2 of tools/models.py) or to 1 (gate: `conv_attenton`), with the
+ *    elementwise chain behind it -- three sigmoids, the scalings, the angle's normalisation -- in ONE launch that reads
+ *    the map once.  Forward only; opt-in from Python (fots_e2e.native.use_native_heads).
+ *
+ *      x        (N, C, H, W)  contiguous NCHW, element type `dtype` (RROI_DTYPE_*)
+ *      w_score  (1, C)   w_rbox (4, C)   w_angle (2, C)    contiguous, the same type: the memory of a (k, C, 1, 1) weight
+ *      b_score  (1)      b_rbox (4)      b_angle (2)       the same type; a NULL bias is +0.0
+ *      score    (N, 1, H, W)   rbox (N, 4, H, W)   angle (N, 2, H, W)   the same type; every element is written and
+ *                             nothing else is; no output may overlap x
+ *      gate:  w (1, C), b (1) or NULL, y (N, 1, H, W)
+ *
+ *    Arithmetic per pixel, fixed so that two identical calls give identical bits:
+ *      every element of x and of the weights is widened exactly to double where it is loaded
+ *      z_o = b_o + p_0 + p_1 + ... + p_{S-1}   added left to right;  p_k = the double sum, from +0.0 in channel order, of
+ *            the exact products w[o][c] * x[c] over the k-th block of ceil(C / S) consecutive channels; S is
+ *            rroi_heads_plan_info.channel_splits
+ *      s_o = 1 / (1 + exp(-z_o))               in double, every operation rounded once (no contraction)
+ *      heads:  score = s_0;  rbox_j = rbox_scale * s_{1+j};  a_i = 2 s_{5+i} - 1,  angle_i = a_i / sqrt(a_0 a_0 + a_1 a_1)
+ *      gate:   y = s_0
+ *      out = (T)(float)value
+ *    -- one rounding to fp32 and one plain conversion to the tensor's type (nearest even, NaN kept), which is how a
+ *    float64 tensor converts; fp32 subnormals are kept on input and output.  a_0 = a_1 = 0 gives NaN in both angle
+ *    channels; a NaN or +-inf in a pixel's channel column affects that pixel alone; a zero weight times an inf is NaN (no
+ *    channel is skipped).  No atomics: the order depends on the plan alone and the plan on (dtype, outputs, N, C, H, W,
+ *    CU count) alone -- 256 CUs where there is no GPU.
+ *    Any element-aligned x, weights and outputs work (a view one element into an allocation is a legal argument).
+ *
+ *    Returns 1 / 0 / -hipError.  0, before any launch: an unknown dtype, a dimension below 1, N * C * H * W >= 2^31, a
+ *    NULL x, weight or output, an rbox_scale that is not finite, `outputs` other than 1 or 7 (plan query).  Each call
+ *    enqueues one kernel on `stream`, uses no workspace, allocates nothing and can be captured into a HIP graph.
+ *    Arrived after 0.10.0 under the same version string: detect it by symbol.
+ * ------------------------------------------------------------------------- */
+typedef struct rroi_heads_plan_info {
+    int vector_elems;    /* V: consecutive pixels per lane (2 or 1) */
+    int channel_splits;  /* S: waves per workgroup, each on its own block of channels (1, 2, 4, 8 or 16; at most 16 / V) */
+    int tiles;           /* tiles of 64 * V pixels per image */
+    int grid_x;          /* workgroups: N * tiles */
+    int block;           /* threads per workgroup: 64 * S */
+    int lds_bytes;       /* (S - 1) * outputs * V * 64 doubles */
+    int channel_block;   /* ceil(C / S) */
+    int reserved;
+} rroi_heads_plan_info;
+int rroi_heads_forward_hip(int dtype, const void* x, const void* w_score, const void* b_score, const void* w_rbox,
+                           const void* b_rbox, const void* w_angle, const void* b_angle, void* score, void* rbox, void* angle,
+                           int batch_size, int channels, int height, int width, double rbox_scale, void* stream);
+int rroi_gate_forward_hip(int dtype, const void* x, const void* w, const void* b, void* y, int batch_size, int channels,
+                          int height, int width, void* stream);
+/* host only, no launch; 1, or 0 for arguments the call would refuse; outputs: 7 (heads) or 1 (gate) */
+int rroi_heads_plan(int dtype, int outputs, int batch_size, int channels, int height, int width, rroi_heads_plan_info* plan);
+
 /* Bin centres only: geom (R, PH, PW, 2) = (bin_cx, bin_cy), 0 where the bin is
  * outside the ROI's pooled width (kernel.cu:86-107).  Diagnostic / test hook. */
 int rroi_align_bin_centres_hip(float spatial_scale, int num_rois, int height, int width,
@@ -586,7 +638,7 @@ int rroi_align_get_trig_recipe_hip(void);
 /* Identification: "rroi_align_hip <version> gfx950" (0.7.0: per-call trig recipe, device-wide setter removed; 0.8.0: launcher scratch reused within a capture, table of 64, stats; 0.9.0: plan query; 0.10.0: bfloat16 / float16 tensors).
  * The typed callers' entry points (rroi_rbox_decode_typed_hip, rroi_ctc_greedy_decode_typed_hip) arrived after 0.10.0 under
  * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b, the depthwise
- * convolution of section 5 and the InstanceNorm of section 6. */
+ * convolution of section 5, the InstanceNorm of section 6 and the heads and gate of section 7. */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
