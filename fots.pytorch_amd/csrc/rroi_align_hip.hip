@@ -588,6 +588,38 @@ int rroi_instancenorm_forward_hip(int dtype, const void* x, const void* gamma, c
     });
 }
 
+// The same norm with an epilogue fused in (header section 6b): the residual add of a block's tail, or the
+// stem's cat(x, -x) in front of it.  The plan is the plain call's for x's shape; neither a residual nor the mirror is
+// the plain call.
+int rroi_instancenorm_fused_forward_hip(int dtype, const void* x, const void* gamma, const void* beta, const void* residual,
+                                        void* y, int batch_size, int channels, int height, int width, int mirror, double eps,
+                                        float negative_slope, void* workspace, size_t workspace_bytes, void* stream_)
+{
+    if (mirror != 0 && mirror != 1) return 0;
+    if (mirror && residual) return 0;
+    if (!mirror && !residual)
+        return rroi_instancenorm_forward_hip(dtype, x, gamma, beta, y, batch_size, channels, height, width, eps, negative_slope,
+                                             workspace, workspace_bytes, stream_);
+    const InormPlan P = plan_instancenorm(dtype, batch_size, channels, height, width, num_cus());
+    if (!P.status) return 0;
+    if (mirror && 2LL * batch_size * channels * height * width >= (1LL << 31)) return 0;   // y's elements (x's are < 2^31)
+    if (!x || !y || (gamma == nullptr) != (beta == nullptr)) return 0;
+    if (!std::isfinite(eps) || !(eps > 0.0) || !std::isfinite(negative_slope)) return 0;
+    if (P.ws_bytes &&
+        (!workspace_ok(workspace) || workspace_bytes < rroi_instancenorm_workspace_bytes(batch_size, channels, height, width)))
+        return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        const T *xt = static_cast<const T*>(x), *g = static_cast<const T*>(gamma), *bt = static_cast<const T*>(beta);
+        if (mirror)
+            return launch_instancenorm_fused<T, kInMirror>(P, xt, g, bt, static_cast<const T*>(nullptr), static_cast<T*>(y),
+                                                           (unsigned)channels, eps, negative_slope, workspace, stream);
+        return launch_instancenorm_fused<T, kInResidual>(P, xt, g, bt, static_cast<const T*>(residual), static_cast<T*>(y),
+                                                         (unsigned)channels, eps, negative_slope, workspace, stream);
+    });
+}
+
 // ------------------------------------------------------------------------------------
 // Detection heads and attention gate of the network (header section 7): one launch, no workspace.
 // ------------------------------------------------------------------------------------

@@ -81,3 +81,23 @@ int launch_instancenorm(const InormPlan& P, const T* x, const T* gamma, const T*
                        P.seg, P.nseg, eps, slope);
     return launch_status();
 }
+
+// The fused epilogues under the same plan, which is the plan of x's shape: the grid runs over x's planes in
+// both modes, and the first launch of the split form is the plain one.
+template <class T, int MODE>
+int launch_instancenorm_fused(const InormPlan& P, const T* x, const T* gamma, const T* beta, const T* r, T* y, unsigned C,
+                              double eps, float slope, void* workspace, hipStream_t stream)
+{
+    if (P.form == RROI_INORM_PLANE) {
+        hipLaunchKernelGGL((rroi_inorm_fused_plane_kernel<T, MODE>), dim3(P.grid), dim3(kInThreads), 0, stream, x, gamma, beta,
+                           r, y, C, P.n, P.planes, eps, slope);
+        return launch_status();
+    }
+    double2* pairs = static_cast<double2*>(workspace);
+    hipLaunchKernelGGL(rroi_inorm_stats_kernel<T>, dim3(P.grid), dim3(kInThreads), 0, stream, x, pairs, P.n, P.seg, P.nseg);
+    const int st = launch_status();
+    if (st != 1) return st;
+    hipLaunchKernelGGL((rroi_inorm_fused_apply_kernel<T, MODE>), dim3(P.grid), dim3(kInThreads), 0, stream, x, gamma, beta, r,
+                       y, pairs, C, P.n, P.seg, P.nseg, eps, slope);
+    return launch_status();
+}

@@ -1,5 +1,6 @@
 """fots_e2e.native -- the operators of FOTSNet that run on the package's own kernels: its depthwise 3x3 convolutions, its
-InstanceNorms (with the activation behind them), and its detection heads and attention gates.
+InstanceNorms (with the activation behind them, the stem's mirror in front of them and the residual add of a block's tail),
+and its detection heads and attention gates.
 
 The 22 depthwise convolutions of the network (`_SeparableBlock.conv_sep1[0]`, `_SeparableBlock.conv2[0]`, `_smooth(...)[0]`
 in upconv1 / upconv2; tools/models.py:70-102 of the reference) are the largest single item of the end-to-end chain's
@@ -18,12 +19,17 @@ The tail of `FOTSNet.forward` -- `_heads` twice per pass (three 1x1 convolutions
 eleven elementwise launches on maps of 1 to 4 channels) and the convolution + sigmoid of `_gate` three times -- is one
 launch per call after `use_native_heads(net)`: `rroi_align._ext.rroi_align.heads` / `gate` wherever `heads_ok`
 holds, the stock methods otherwise.  The bilinear resize behind the gate stays stock.  The same terms once more.
+
+What `model.py` applies functionally around its norms -- the stem's `cat(x, -x)` and LeakyReLU in `_MirrorNorm` (twice per
+pass, on the two largest tensors of the network), the ReLU behind `_PlainBlock.bn1`, and the shortcut add and activation
+of all 17 residual blocks -- is folded into the norm's own launch after `use_native_blocks(net)`:
+`rroi_align._ext.rroi_align.instance_norm_fused` wherever `fused_norm_ok` holds, the stock forward otherwise.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .model import FOTSNet
+from .model import FOTSNet, _MirrorNorm, _PlainBlock, _SeparableBlock
 
 _DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
@@ -84,9 +90,14 @@ def instancenorm_ok(m, x) -> bool:
     """True where `m(x)` may run the native kernel: pure, no GPU needed to ask.  Instance statistics only (a module that
     tracks running statistics keeps the stock path, in training and in eval; so does a plane of one element, which the
     stock module refuses with a ValueError)."""
+    return _inorm_ok(m, x, 1)
+
+
+def _inorm_ok(m, x, widen) -> bool:
+    """`instancenorm_ok` for a norm of `widen` times x's channels (2: the stem's mirror, which widens x on the way in)."""
     w = m._parameters.get("weight")
     return (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype in _DTYPES and x.is_contiguous()
-            and not m.track_running_stats and x.size(1) == m.num_features and 0 < x.numel() < (1 << 31)
+            and not m.track_running_stats and widen * x.size(1) == m.num_features and 0 < widen * x.numel() < (1 << 31)
             and x.size(2) * x.size(3) > 1 and not _inorm_slower(x)
             and (w is None or (w.dtype == x.dtype and w.device == x.device and m._parameters.get("bias") is not None))
             and not torch.is_autocast_enabled()
@@ -237,3 +248,106 @@ def use_native_heads(net: nn.Module, enable: bool = True) -> bool:
         return False
     net.__class__ = dst
     return True
+
+
+# --------------------------------------------------------------------------- the stem's mirror and the blocks' tails, DESIGN 5.13
+def fused_norm_ok(norm, t, residual=None, mirror: bool = False) -> bool:
+    """True where `norm` on `t` may run `rroi_align._ext.rroi_align._instance_norm_fused_run` (with neither a residual
+    nor the mirror: `_instance_norm_run` with a slope of the caller's): pure, no GPU needed to ask.  It is
+    `instancenorm_ok(norm, t)` and
+      residual   a contiguous tensor of t's shape, dtype and device that needs no gradient;
+      mirror     an affine norm of twice t's channels, whose output stays below 2^31 elements;
+      a norm to which `use_native_instancenorm` has given a `fused_slope` applies an activation of its own: declined."""
+    if getattr(norm, "fused_slope", None) is not None:
+        return False
+    if mirror:
+        return residual is None and norm._parameters.get("weight") is not None and _inorm_ok(norm, t, 2)
+    if not _inorm_ok(norm, t, 1):
+        return False
+    return residual is None or (
+        isinstance(residual, torch.Tensor) and residual.is_cuda and residual.shape == t.shape and residual.dtype == t.dtype
+        and residual.device == t.device and residual.is_contiguous()
+        and not (torch.is_grad_enabled() and residual.requires_grad))
+
+
+def _block_input_ok(block, x) -> bool:
+    """What can be asked before a block computes anything: where this fails, no predicate further down can hold, and the
+    stock forward runs without anything having been computed twice.  (A block in training mode is left to the stock code
+    whatever its input: the BatchNorm of a shortcut keeps running statistics.  Under grad mode the block's first
+    parameter stands for all of them; under `torch.no_grad()`, where the pipeline runs, none is looked at.)"""
+    return (not block.training and isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype in _DTYPES
+            and x.numel() > 0 and not torch.is_autocast_enabled()
+            and not (torch.is_grad_enabled() and (x.requires_grad or next(block.parameters()).requires_grad)))
+
+
+def _affine(norm):
+    p = norm._parameters
+    return p.get("weight"), p.get("bias")
+
+
+class NativeMirrorNorm(_MirrorNorm):
+    """A `_MirrorNorm` (same module, same `state_dict` keys) whose negation, concatenation, norm and LeakyReLU are one
+    native call where `fused_norm_ok(self.bn, x, mirror=True)` holds."""
+
+    def forward(self, x):
+        bn = self.bn
+        if fused_norm_ok(bn, x, mirror=True):
+            return _ext()._instance_norm_fused_run(x, *_affine(bn), bn.eps, 0.01, None, True)
+        return super().forward(x)
+
+
+class NativePlainBlock(_PlainBlock):
+    """A `_PlainBlock` whose `bn1` + ReLU is one native call and whose `bn2` + shortcut + ReLU is another, where
+    `fused_norm_ok` holds for both; the stock forward otherwise (what a late refusal had computed is computed again by
+    it: the stock code is not restated here)."""
+
+    def forward(self, x):
+        if not _block_input_ok(self, x):
+            return super().forward(x)
+        bn1, bn2 = self.bn1, self.bn2
+        t = self.conv1(x)
+        if not fused_norm_ok(bn1, t):
+            return super().forward(x)
+        t = self.conv2(_ext()._instance_norm_run(t, *_affine(bn1), bn1.eps, 0.0))
+        r = x if self.downsample is None else self.downsample(x)
+        if not fused_norm_ok(bn2, t, residual=r):
+            return super().forward(x)
+        return _ext()._instance_norm_fused_run(t, *_affine(bn2), bn2.eps, float(self.slope), r, False)
+
+
+class NativeSeparableBlock(_SeparableBlock):
+    """A `_SeparableBlock` whose last norm, shortcut add and LeakyReLU are one native call where `fused_norm_ok` holds.
+    The modules of `conv2` in front of that norm run as they are, so what `use_native_depthwise` and
+    `use_native_instancenorm` made of them -- absorbed activations included -- keeps working."""
+
+    def forward(self, x):
+        if not _block_input_ok(self, x):
+            return super().forward(x)
+        t = self.conv_sep1(x)
+        body = list(self.conv2._modules.values())
+        for m in body[:-1]:
+            t = m(t)
+        last = body[-1]
+        r = x if self.downsample is None else self.downsample(x)
+        if not (isinstance(last, nn.InstanceNorm2d) and fused_norm_ok(last, t, residual=r)):
+            return super().forward(x)
+        return _ext()._instance_norm_fused_run(t, *_affine(last), last.eps, float(self.slope), r, False)
+
+
+_BLOCKS = ((_MirrorNorm, NativeMirrorNorm), (_PlainBlock, NativePlainBlock), (_SeparableBlock, NativeSeparableBlock))
+
+
+def use_native_blocks(net: nn.Module, enable: bool = True):
+    """Switch every `_MirrorNorm`, `_PlainBlock` and `_SeparableBlock` of `net` -- by exact type -- to its native subclass
+    (enable=False: back).  Only classes change: no parameter is copied, no key of the state_dict moves; the switches above
+    compose with this one in any order.  Returns (mirror norms, plain blocks, separable blocks) switched: (2, 7, 10) for
+    `FOTSNet()`."""
+    counts = [0, 0, 0]
+    for m in net.modules():
+        for k, (stock, native) in enumerate(_BLOCKS):
+            src, dst = (stock, native) if enable else (native, stock)
+            if type(m) is src:
+                m.__class__ = dst
+                counts[k] += 1
+                break
+    return tuple(counts)

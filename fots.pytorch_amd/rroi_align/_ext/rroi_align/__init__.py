@@ -158,6 +158,9 @@ _lib.rroi_instancenorm_workspace_bytes.argtypes = [_i] * 4
 _lib.rroi_instancenorm_plan.restype = _i
 _lib.rroi_instancenorm_plan.argtypes = [_i] * 5 + [ctypes.POINTER(_InormPlan)]
 INORM_PLANE, INORM_SPLIT = 1, 2
+# ... with the residual add or the stem's mirror fused in (header section 6b; found by symbol likewise)
+_lib.rroi_instancenorm_fused_forward_hip.restype = _i
+_lib.rroi_instancenorm_fused_forward_hip.argtypes = [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _f, _vp, _sz, _vp]
 # the network's detection heads and attention gate (header section 7; after 0.10.0, same version string: found by symbol)
 
 
@@ -194,6 +197,7 @@ EXPORTS = (
     "rroi_depthwise3x3_forward_hip",
     "rroi_instancenorm_forward_hip", "rroi_instancenorm_workspace_bytes", "rroi_instancenorm_plan",
     "rroi_heads_forward_hip", "rroi_gate_forward_hip", "rroi_heads_plan",
+    "rroi_instancenorm_fused_forward_hip",
 )
 
 # What a call launches (rroi_align_forward_plan / rroi_align_backward_plan); the fields of rroi_align_plan.
@@ -774,6 +778,85 @@ def _instance_norm_run(x: torch.Tensor, weight, bias, eps: float, negative_slope
                                             negative_slope, None if ws is None else ws.data_ptr(), nbytes, _stream())
     if st != 1:
         _check(st, "rroi_instancenorm_forward_hip")
+    return out
+
+
+def instance_norm_fused(x: torch.Tensor, weight=None, bias=None, eps: float = 1e-5, negative_slope: float = 1.0,
+                        residual=None, mirror: bool = False) -> torch.Tensor:
+    """`instance_norm` with an epilogue fused in -- DESIGN 5.13.
+    residual (x's shape, dtype and device):  act(instance_norm(x) + residual), the sum in fp32 and rounded once: the tail
+    of a residual block in one call.
+    mirror:  the InstanceNorm2d of `torch.cat((x, -x), 1)` with its activation, without the concatenation: (N,2C,H,W) from
+    (N,C,H,W); weight and bias are (2C,) or both None.  Not together with a residual.
+    With neither, `instance_norm`.  The same exceptions as `instance_norm`; ValueError also for a residual whose shape,
+    dtype or device is not x's, for mirror together with a residual, and for a weight that is not (2C,) under mirror."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a torch.Tensor")
+    if x.dim() != 4:
+        raise ValueError(f"x must be (N,C,H,W), got {tuple(x.shape)}")
+    if (weight is None) != (bias is None):
+        raise ValueError("weight and bias come together, or neither")
+    mirror = bool(mirror)
+    if mirror and residual is not None:
+        raise ValueError("mirror takes no residual")
+    features = x.size(1) * (2 if mirror else 1)
+    for name, p in (("weight", weight), ("bias", bias)):
+        if p is None:
+            continue
+        if not isinstance(p, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if tuple(p.shape) != (features,):
+            raise ValueError(f"{name} must be {(features,)} for x {tuple(x.shape)}{' mirrored' if mirror else ''}, "
+                             f"got {tuple(p.shape)}")
+        if p.dtype != x.dtype:
+            raise ValueError(f"x and {name} must have one dtype, got {x.dtype} and {p.dtype}")
+    if residual is not None:
+        if not isinstance(residual, torch.Tensor):
+            raise TypeError("residual must be a torch.Tensor")
+        if residual.shape != x.shape:
+            raise ValueError(f"residual must have x's shape {tuple(x.shape)}, got {tuple(residual.shape)}")
+        if residual.dtype != x.dtype:
+            raise ValueError(f"x and residual must have one dtype, got {x.dtype} and {residual.dtype}")
+        if residual.device != x.device:
+            raise ValueError("x and residual must be on the same device")
+    _require_cuda_f32(x, "x", _IO_DTYPES)
+    for name, p in (("weight", weight), ("bias", bias)):
+        if p is not None:
+            _require_cuda_f32(p, name, _IO_DTYPES)
+            if p.device != x.device:
+                raise ValueError(f"x and {name} must be on the same device")
+    if features < 1 or x.size(2) < 1 or x.size(3) < 1:
+        raise ValueError(f"x must have at least one channel, row and column, got {tuple(x.shape)}")
+    if mirror and 2 * x.numel() >= 1 << 31:
+        raise ValueError(f"the mirrored output of x {tuple(x.shape)} has 2^31 elements or more")
+    if weight is not None:
+        weight, bias = weight.contiguous(), bias.contiguous()
+    if residual is None and not mirror:
+        return _instance_norm_run(x.contiguous(), weight, bias, float(eps), float(negative_slope))
+    return _instance_norm_fused_run(x.contiguous(), weight, bias, float(eps), float(negative_slope),
+                                    None if residual is None else residual.contiguous(), mirror)
+
+
+def _instance_norm_fused_run(x: torch.Tensor, weight, bias, eps: float, negative_slope: float, residual, mirror: bool) -> torch.Tensor:
+    """The call itself, for arguments already checked (instance_norm_fused above; fots_e2e.native after fused_norm_ok): as
+    `_instance_norm_run`, with `residual` a contiguous tensor like x or None, and under `mirror` weight and bias (2C,) and
+    no residual.  Kept lean for the same reason."""
+    index = x.device.index
+    if index != torch.cuda.current_device():
+        with torch.cuda.device(index):
+            return _instance_norm_fused_run(x, weight, bias, eps, negative_slope, residual, mirror)
+    N, C, H, W = x.shape
+    out = torch.empty((N, 2 * C, H, W), dtype=x.dtype, device=x.device) if mirror else torch.empty_like(x)
+    if N == 0:
+        return out
+    nbytes = _lib.rroi_instancenorm_workspace_bytes(N, C, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    st = _lib.rroi_instancenorm_fused_forward_hip(
+        _DTYPES[x.dtype], x.data_ptr(), None if weight is None else weight.data_ptr(), None if bias is None else bias.data_ptr(),
+        None if residual is None else residual.data_ptr(), out.data_ptr(), N, C, H, W, 1 if mirror else 0, eps, negative_slope,
+        None if ws is None else ws.data_ptr(), nbytes, _stream())
+    if st != 1:
+        _check(st, "rroi_instancenorm_fused_forward_hip")
     return out
 
 

@@ -557,6 +557,38 @@ size_t rroi_instancenorm_workspace_bytes(int batch_size, int channels, int heigh
 int rroi_instancenorm_plan(int dtype, int batch_size, int channels, int height, int width, rroi_instancenorm_plan_info* plan);
 
 /* ------------------------------------------------------------------------- *
+ * 6b. The InstanceNorm of section 6 with an epilogue fused in: the residual add in the tail of the
+ *    network's residual blocks, or the concatenation cat(x, -x) in front of the stem's two norms (`CReLU_IN` of
+ *    tools/models.py).  Forward only; opt-in from Python (fots_e2e.native.use_native_blocks).
+ *
+ *      x        (N, C, H, W)   as in section 6; `channels` is x's channel count in both modes
+ *      residual (N, C, H, W)   the same type, or NULL
+ *      mirror   0 / 1
+ *      mirror = 0:  gamma, beta (C) or both NULL, y (N, C, H, W):
+ *          v = (float)((double)x * a + b);  u = v + (float)residual  (fp32, rounded once);
+ *          u = u < 0 ? u * negative_slope : u;  y = (T)u
+ *        With residual = NULL this is the call of section 6.
+ *      mirror = 1:  gamma, beta (2C) or both NULL, y (N, 2C, H, W), residual NULL:  y = what section 6 gives on
+ *        cat(x, -x) along the channels, which is never materialised.  Source plane (n, j) is summed once, as in section 6;
+ *        output plane (n, j) takes (K, s1, s2) with gamma[j], beta[j], and output plane (n, C + j) takes (-K, -s1, s2) --
+ *        exactly the sums of the negated plane -- with gamma[C + j], beta[C + j].  The bits are those of the section 6
+ *        call on the concatenated tensor whenever that call adds in the same order: the same form and segment length,
+ *        and every plane of both tensors at the same offset from a 16-byte boundary.
+ *    The statistics, their order and the workspace are those of section 6 for x's shape: rroi_instancenorm_plan and
+ *    rroi_instancenorm_workspace_bytes called with (N, C, H, W) of x answer for this entry point too.  A NaN or +-inf in
+ *    the residual affects its own element alone; one in a plane of x takes that plane and, under mirror, both its
+ *    output planes.  y must not overlap x or residual.  Any element-aligned x, residual and y work.
+ *
+ *    Returns 1 / 0 / -hipError.  0, before any launch: everything section 6 refuses, a mirror other than 0 or 1,
+ *    mirror = 1 with a non-NULL residual, mirror = 1 with N * 2C * H * W >= 2^31.  The call only enqueues on `stream`,
+ *    allocates nothing and can be captured into a HIP graph.  Arrived after 0.10.0 under the same version string: detect
+ *    it by symbol.
+ * ------------------------------------------------------------------------- */
+int rroi_instancenorm_fused_forward_hip(int dtype, const void* x, const void* gamma, const void* beta, const void* residual,
+                                        void* y, int batch_size, int channels, int height, int width, int mirror, double eps,
+                                        float negative_slope, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * 7. The network's detection heads and attention gate: a 1x1 convolution with bias from many channels to
  *    7 outputs (heads: `act` 1, `rbox` 4, `angle` 2 of tools/models.py) or to 1 (gate: `conv_attenton`), with the
  *    elementwise chain behind it -- three sigmoids, the scalings, the angle's normalisation -- in ONE launch that reads
@@ -638,7 +670,7 @@ int rroi_align_get_trig_recipe_hip(void);
 /* Identification: "rroi_align_hip <version> gfx950" (0.7.0: per-call trig recipe, device-wide setter removed; 0.8.0: launcher scratch reused within a capture, table of 64, stats; 0.9.0: plan query; 0.10.0: bfloat16 / float16 tensors).
  * The typed callers' entry points (rroi_rbox_decode_typed_hip, rroi_ctc_greedy_decode_typed_hip) arrived after 0.10.0 under
  * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b, the depthwise
- * convolution of section 5, the InstanceNorm of section 6 and the heads and gate of section 7. */
+ * convolution of section 5, the InstanceNorm of section 6, its fused epilogues of section 6b and the heads and gate of section 7. */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
