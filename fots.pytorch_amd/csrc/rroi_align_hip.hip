@@ -28,7 +28,8 @@
 // rroi_callers_kernels.h, rroi_nms_kernels.h (+ rroi_nms_host.h, host C++), rroi_depthwise_kernels.h (+ rroi_depthwise_host.h:
 // the network's depthwise 3x3 convolution), rroi_instancenorm_kernels.h (+ rroi_instancenorm_host.h: its
 // InstanceNorm2d with the activation behind it), rroi_heads_kernels.h (+ rroi_heads_host.h: its detection heads
-// and attention gate).  Host side: rroi_host_plan.h (tuning table,
+// and attention gate), rroi_merge_kernels.h (+ rroi_merge_host.h: the gated merge of its feature merge,
+// DESIGN 5.14).  Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
 // launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
 #include <hip/hip_runtime.h>
@@ -60,6 +61,7 @@ namespace {
 #include "rroi_depthwise_kernels.h"
 #include "rroi_instancenorm_kernels.h"
 #include "rroi_heads_kernels.h"
+#include "rroi_merge_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
@@ -67,6 +69,7 @@ namespace {
 #include "rroi_depthwise_host.h"
 #include "rroi_instancenorm_host.h"
 #include "rroi_heads_host.h"
+#include "rroi_merge_host.h"
 
 }  // namespace
 
@@ -690,6 +693,55 @@ int rroi_gate_forward_hip(int dtype, const void* x, const void* w, const void* b
                                                      static_cast<T*>(nullptr), (unsigned)channels, 1.0, stream);
     });
 }
+
+// ------------------------------------------------------------------------------------
+// Gated merge of the network's feature merge (header section 8): y = A + f * G, one launch, no workspace.
+// ------------------------------------------------------------------------------------
+int rroi_merge_plan(int dtype, int batch_size, int channels, int height, int width, int a_h, int a_w, int g_h, int g_w,
+                    int gated, rroi_merge_plan_info* plan)
+{
+    const MergePlan P = plan_merge(dtype, batch_size, channels, height, width, a_h, a_w, g_h, g_w, gated, num_cus());
+    if (!P.status || !plan) return 0;
+    *plan = rroi_merge_plan_info{P.V, P.K, (int)P.tiles, (int)P.grid, kMgThreads, (int)P.cb, P.resize_a ? 1 : 0,
+                                 P.resize_g ? 1 : 0, P.A.sy, P.A.sx, P.G.sy, P.G.sx};
+    return 1;
+}
+
+static int merge_impl(const MergePlan& P, int dtype, const void* a, const void* gate, const void* f, void* y, int channels,
+                      int width, void* stream_)
+{
+    if (!P.status) return 0;
+    if (!a || !f || !y) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_merge(P, static_cast<const T*>(a), static_cast<const T*>(gate), static_cast<const T*>(f),
+                            static_cast<T*>(y), (unsigned)channels, (unsigned)width, stream);
+    });
+}
+
+int rroi_merge_forward_hip(int dtype, const void* a, int a_h, int a_w, const void* gate, int g_h, int g_w, const void* f,
+                           void* y, int batch_size, int channels, int height, int width, void* stream)
+{
+    return merge_impl(plan_merge(dtype, batch_size, channels, height, width, a_h, a_w, g_h, g_w, gate ? 1 : 0, num_cus()), dtype,
+                      a, gate, f, y, channels, width, stream);
+}
+
+#ifdef RROI_MERGE_MEASURE
+// Measurement build only (`make merge-forms`; not declared in the header, not in the shipped library): the merge with V
+// and K forced, for the comparison of the plan rule against its neighbours (tools/merge_bench.py --forms).
+// *v_used / *k_used report what ran.
+int rroi_merge_forward_forced_hip(int dtype, const void* a, int a_h, int a_w, const void* gate, int g_h, int g_w,
+                                  const void* f, void* y, int batch_size, int channels, int height, int width, int force_v,
+                                  int force_k, int* v_used, int* k_used, void* stream)
+{
+    const MergePlan P = plan_merge(dtype, batch_size, channels, height, width, a_h, a_w, g_h, g_w, gate ? 1 : 0, num_cus(),
+                                   force_v, force_k);
+    if (v_used) *v_used = P.V;
+    if (k_used) *k_used = P.K;
+    return merge_impl(P, dtype, a, gate, f, y, channels, width, stream);
+}
+#endif
 
 int rroi_align_set_trig_recipe_hip(int recipe) { return recipe == RROI_TRIG_DOUBLE ? 1 : 0; }   // deprecated shim, see the header
 int rroi_align_get_trig_recipe_hip(void) { return RROI_TRIG_DOUBLE; }

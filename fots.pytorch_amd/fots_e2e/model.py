@@ -148,16 +148,8 @@ class FOTSNet(nn.Module):
         ang = ang / torch.sqrt(ang[:, 0] * ang[:, 0] + ang[:, 1] * ang[:, 1]).unsqueeze(1)
         return score, dist, ang
 
-    def forward(self, x):
-        """-> [score, score_1/8], [rbox, rbox_1/8], [angle, angle_1/8], [merged 256-ch 1/4 map, focr]
-        (models.py:387-457)."""
-        focr = self.forward_features(x)
-        c1 = self.layer1(self.drop1(focr))
-        c2 = self.layer2(c1)
-        c3 = self.layer3(c2)
-        c4 = self.drop1(self.layer4(c3))
-        f1, f2, f3, f4 = self.feature1(c1), self.feature2(c2), self.feature3(c3), self.feature4(c4)
-
+    def _merge(self, f1, f2, f3, f4):
+        """The feature merge (models.py:412-440): -> (merged 1/4 map, merged 1/8 map)."""
         if self.attention:
             # the first gate is expanded to 256 identical channels before it is resized (:413-415)
             t = self._up(f4, f3) + f3 * self._gate(f4, f3).expand_as(f3)
@@ -169,6 +161,19 @@ class FOTSNet(nn.Module):
             t = self._up(f4, f3) + f3
             m2 = self.upconv1(self._up(t, f2)) + f2
             m1 = self.upconv2(self._up(m2, f1)) + f1
+        return m1, m2
+
+    def forward(self, x):
+        """-> [score, score_1/8], [rbox, rbox_1/8], [angle, angle_1/8], [merged 256-ch 1/4 map, focr]
+        (models.py:387-457)."""
+        focr = self.forward_features(x)
+        c1 = self.layer1(self.drop1(focr))
+        c2 = self.layer2(c1)
+        c3 = self.layer3(c2)
+        c4 = self.drop1(self.layer4(c3))
+        f1, f2, f3, f4 = self.feature1(c1), self.feature2(c2), self.feature3(c3), self.feature4(c4)
+
+        m1, m2 = self._merge(f1, f2, f3, f4)
         s8, r8, a8 = self._heads(m2)
         m1 = self.drop1(m1)
         s4, r4, a4 = self._heads(m1)

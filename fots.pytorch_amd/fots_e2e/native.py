@@ -1,6 +1,6 @@
 """fots_e2e.native -- the operators of FOTSNet that run on the package's own kernels: its depthwise 3x3 convolutions, its
 InstanceNorms (with the activation behind them, the stem's mirror in front of them and the residual add of a block's tail),
-and its detection heads and attention gates.
+its detection heads and attention gates, and the gated merges of its feature merge.
 
 The 22 depthwise convolutions of the network (`_SeparableBlock.conv_sep1[0]`, `_SeparableBlock.conv2[0]`, `_smooth(...)[0]`
 in upconv1 / upconv2; tools/models.py:70-102 of the reference) are the largest single item of the end-to-end chain's
@@ -18,7 +18,12 @@ followed by its activation inside an `nn.Sequential` apply that activation itsel
 The tail of `FOTSNet.forward` -- `_heads` twice per pass (three 1x1 convolutions that each read the 256-channel map, and
 eleven elementwise launches on maps of 1 to 4 channels) and the convolution + sigmoid of `_gate` three times -- is one
 launch per call after `use_native_heads(net)`: `rroi_align._ext.rroi_align.heads` / `gate` wherever `heads_ok`
-holds, the stock methods otherwise.  The bilinear resize behind the gate stays stock.  The same terms once more.
+holds, the stock methods otherwise.  The same terms once more.
+
+The feature merge between them -- three times `up(a) + f * up(gate)`: a bilinear resize of the one-channel gate, a multiply
+and an add over a 256-channel map, in the first merge also a resize of the coarser map -- is one launch per merge after
+`use_native_merge(net)`: `rroi_align._ext.rroi_align.gated_merge` wherever `merge_ok` holds, the stock
+expression otherwise.  The resize in front of `upconv1` / `upconv2` and the `upconv` blocks stay stock.
 
 What `model.py` applies functionally around its norms -- the stem's `cat(x, -x)` and LeakyReLU in `_MirrorNorm` (twice per
 pass, on the two largest tensors of the network), the ReLU behind `_PlainBlock.bn1`, and the shortcut add and activation
@@ -239,15 +244,88 @@ class NativeHeadsFOTSNet(FOTSNet):
         return super()._gate(t, like)
 
 
+def _switch_class(net, pairs, enable) -> bool:
+    """`net.__class__` from the first to the second class of the pair whose first (enable=False: second) is exactly its type."""
+    for stock, native in pairs:
+        src, dst = (stock, native) if enable else (native, stock)
+        if type(net) is src:
+            net.__class__ = dst
+            return True
+    return False
+
+
 def use_native_heads(net: nn.Module, enable: bool = True) -> bool:
-    """Switch a network whose type is exactly `FOTSNet` to `NativeHeadsFOTSNet` (enable=False: back).  Only the class of
-    the network changes: no parameter is copied, no key of the state_dict moves; the module switches above compose with it
-    in any order.  A network of any other type is left alone.  Returns whether the class was switched."""
-    src, dst = (FOTSNet, NativeHeadsFOTSNet) if enable else (NativeHeadsFOTSNet, FOTSNet)
-    if type(net) is not src:
+    """Switch a network whose type is exactly `FOTSNet` to `NativeHeadsFOTSNet` (enable=False: back), and one that
+    `use_native_merge` has switched, `NativeMergeFOTSNet`, to `NativeHeadsMergeFOTSNet`.  Only the class of the network
+    changes: no parameter is copied, no key of the state_dict moves; the module switches above and `use_native_merge`
+    compose with it in any order.  A network of any other type is left alone.  Returns whether the class was switched."""
+    return _switch_class(net, ((FOTSNet, NativeHeadsFOTSNet), (NativeMergeFOTSNet, NativeHeadsMergeFOTSNet)), enable)
+
+
+# --------------------------------------------------------------------------- the feature merge, DESIGN 5.14
+def merge_ok(a, f, gate=None) -> bool:
+    """True where `up(a) + f * up(gate)` (gate=None: `up(a) + f`) may run the native kernel: pure, no GPU needed to ask.
+    CUDA tensors that are 4-D, contiguous, of one of the three dtypes, all of one dtype and device, `a` with f's batch
+    size and channels, a one-channel gate with f's batch size, each of fewer than 2^31 elements, no autocast, no
+    gradient needed."""
+    ts = (f, a) if gate is None else (f, a, gate)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 4 and t.is_contiguous() and 0 < t.numel() < (1 << 31)
+               for t in ts):
         return False
-    net.__class__ = dst
-    return True
+    return (f.dtype in _DTYPES and all(t.dtype == f.dtype and t.device == f.device for t in ts[1:])
+            and a.shape[:2] == f.shape[:2] and (gate is None or (gate.size(0) == f.size(0) and gate.size(1) == 1))
+            and not _merge_slower(a, f, gate)
+            and not torch.is_autocast_enabled()
+            and not (torch.is_grad_enabled() and any(t.requires_grad for t in ts)))
+
+
+def _merge_slower(a, f, gate) -> bool:
+    """The shape classes in which the native kernel measured slower than the stock chain (profiles/native_merge.md): none."""
+    return False
+
+
+class _NativeMerge:
+    """Mixin in front of a `FOTSNet`: `_merge` runs each of the three merges, `up(a) + f * up(gate)`, as one native call
+    where `merge_ok` holds, and as the stock expression where it does not.  The resize in front of `upconv1` / `upconv2`
+    stays stock.  A network in training mode takes the stock method."""
+
+    def _low_gate(self, t):
+        """The gate at its source's size, before the resize: the native gate where the network has it."""
+        if isinstance(self, NativeHeadsFOTSNet) and heads_ok(self, t, gate=True):
+            return _ext()._gate_run(t, *_wb(self.conv_attenton))
+        return torch.sigmoid(self.conv_attenton(t))
+
+    def _merge_one(self, a, f, t):
+        """up(a) + f * up(gate of t), or up(a) + f for a network without attention; `a` of f's size is not resized."""
+        g = self._low_gate(t) if self.attention else None
+        if merge_ok(a, f, g):
+            return _ext()._gated_merge_run(a, f, g)
+        A = a if a.shape[2:] == f.shape[2:] else self._up(a, f)
+        return A + f if g is None else A + f * self._up(g, f)
+
+    def _merge(self, f1, f2, f3, f4):
+        if self.training:
+            return super()._merge(f1, f2, f3, f4)
+        t = self._merge_one(f4, f3, f4)
+        m2 = self._merge_one(self.upconv1(self._up(t, f2)), f2, t)
+        m1 = self._merge_one(self.upconv2(self._up(m2, f1)), f1, m2)
+        return m1, m2
+
+
+class NativeMergeFOTSNet(_NativeMerge, FOTSNet):
+    """A `FOTSNet` (same modules, same `state_dict` keys) whose three merges run the native kernel where `merge_ok` holds."""
+
+
+class NativeHeadsMergeFOTSNet(_NativeMerge, NativeHeadsFOTSNet):
+    """A `NativeHeadsFOTSNet` with the native merges: the gate kernel's output goes into the merge at its own size."""
+
+
+def use_native_merge(net: nn.Module, enable: bool = True) -> bool:
+    """Switch a network whose type is exactly `FOTSNet` to `NativeMergeFOTSNet`, or exactly `NativeHeadsFOTSNet` to
+    `NativeHeadsMergeFOTSNet` (enable=False: back).  Only the class of the network changes: no parameter is copied, no key
+    of the state_dict moves; it composes with `use_native_heads` and the module switches in any order.  A network of any
+    other type is left alone.  Returns whether the class was switched."""
+    return _switch_class(net, ((FOTSNet, NativeMergeFOTSNet), (NativeHeadsFOTSNet, NativeHeadsMergeFOTSNet)), enable)
 
 
 # --------------------------------------------------------------------------- the stem's mirror and the blocks' tails, DESIGN 5.13

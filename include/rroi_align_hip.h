@@ -640,6 +640,50 @@ int rroi_gate_forward_hip(int dtype, const void* x, const void* w, const void* b
 /* host only, no launch; 1, or 0 for arguments the call would refuse; outputs: 7 (heads) or 1 (gate) */
 int rroi_heads_plan(int dtype, int outputs, int batch_size, int channels, int height, int width, rroi_heads_plan_info* plan);
 
+/* ------------------------------------------------------------------------- *
+ * 8. The gated merge of the network's feature merge: y = A + f * G in ONE launch, where A is `a` resized
+ *    to f's size and G the one-channel `gate` resized likewise -- `up(a) + f * up(gate)` of tools/models.py:412-434.
+ *    Forward only; opt-in from Python (fots_e2e.native.use_native_merge).
+ *
+ *      a      (N, C, a_h, a_w)      gate   (N, 1, g_h, g_w) or NULL: y = A + f (g_h, g_w are not read)
+ *      f, y   (N, C, H, W)          all contiguous NCHW, one element type `dtype` (RROI_DTYPE_*)
+ *    Every element of y is written and nothing else is; y may overlap no input.
+ *
+ *    Resize: bilinear, align_corners = true, in double.  Per axis s = (double)(in - 1) / (double)(out - 1), 0 where
+ *    out == 1, computed on the host (rroi_merge_plan_info.*_scale_*);
+ *      src = s * (double)dst;  i0 = min((int)src, in - 1);  i1 = min(i0 + 1, in - 1);  l1 = src - i0;  l0 = 1.0 - l1
+ *      value = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11)
+ *    every multiply and add rounded separately to double in exactly that order (no contraction), every tap widened
+ *    exactly to double where it is loaded, no tap skipped (a zero weight against an infinity is NaN).  A source whose
+ *    size equals (H, W) on both axes is read as it is, with no interpolation arithmetic.
+ *    Sum: p = (double)f * G;  z = A + p (no gate: z = A + (double)f);  out = (T)(float)z -- one rounding to fp32 and one
+ *    plain conversion to the tensor's type, as in sections 6 and 7; fp32 subnormals are kept; a gate value outside [0, 1] is
+ *    used as it is.  Nothing is transcendental and nothing is reduced across lanes: the bits depend on neither the plan nor
+ *    an address, and a float64 restatement with separate multiplies and adds reproduces every element bit for bit.
+ *    Any element-aligned a, gate, f and y work.
+ *
+ *    Returns 1 / 0 / -hipError.  0, before any launch: an unknown dtype, a dimension below 1 (g_h, g_w: with a gate),
+ *    N * C * H * W >= 2^31, N * C * a_h * a_w >= 2^31, N * g_h * g_w >= 2^31, a NULL a, f or y, `gated` other than 0 or 1
+ *    (plan query).  Each call enqueues one kernel on `stream`, uses no workspace, allocates nothing and can be captured
+ *    into a HIP graph.  Arrived after 0.10.0 under the same version string: detect it by symbol.
+ * ------------------------------------------------------------------------- */
+typedef struct rroi_merge_plan_info {
+    int vector_elems;    /* V: consecutive pixels per lane (4; 2 where a is resized) */
+    int channel_groups;  /* K: workgroups per tile, each on its own block of channels */
+    int tiles;           /* tiles of 256 * V pixels per image */
+    int grid_x;          /* workgroups: N * K * tiles */
+    int block;           /* threads per workgroup: 256 */
+    int channel_block;   /* ceil(C / K) */
+    int resize_a;        /* 1: a is interpolated; 0: it has f's size and is read as it is */
+    int resize_gate;     /* likewise for the gate (0 without one) */
+    double a_scale_y, a_scale_x, gate_scale_y, gate_scale_x;   /* s per axis (the gate's: 0 without one) */
+} rroi_merge_plan_info;
+int rroi_merge_forward_hip(int dtype, const void* a, int a_h, int a_w, const void* gate, int g_h, int g_w, const void* f,
+                           void* y, int batch_size, int channels, int height, int width, void* stream);
+/* host only, no launch; 1, or 0 for arguments the call would refuse; gated: 1 (g_h, g_w are the gate's size) or 0 */
+int rroi_merge_plan(int dtype, int batch_size, int channels, int height, int width, int a_h, int a_w, int g_h, int g_w,
+                    int gated, rroi_merge_plan_info* plan);
+
 /* Bin centres only: geom (R, PH, PW, 2) = (bin_cx, bin_cy), 0 where the bin is
  * outside the ROI's pooled width (kernel.cu:86-107).  Diagnostic / test hook. */
 int rroi_align_bin_centres_hip(float spatial_scale, int num_rois, int height, int width,
@@ -670,7 +714,8 @@ int rroi_align_get_trig_recipe_hip(void);
 /* Identification: "rroi_align_hip <version> gfx950" (0.7.0: per-call trig recipe, device-wide setter removed; 0.8.0: launcher scratch reused within a capture, table of 64, stats; 0.9.0: plan query; 0.10.0: bfloat16 / float16 tensors).
  * The typed callers' entry points (rroi_rbox_decode_typed_hip, rroi_ctc_greedy_decode_typed_hip) arrived after 0.10.0 under
  * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b, the depthwise
- * convolution of section 5, the InstanceNorm of section 6, its fused epilogues of section 6b and the heads and gate of section 7. */
+ * convolution of section 5, the InstanceNorm of section 6, its fused epilogues of section 6b, the heads and gate of section 7 and the gated merge
+ * of section 8. */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
