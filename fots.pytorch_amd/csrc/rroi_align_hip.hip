@@ -29,7 +29,8 @@
 // the network's depthwise 3x3 convolution), rroi_instancenorm_kernels.h (+ rroi_instancenorm_host.h: its
 // InstanceNorm2d with the activation behind it), rroi_heads_kernels.h (+ rroi_heads_host.h: its detection heads
 // and attention gate), rroi_merge_kernels.h (+ rroi_merge_host.h: the gated merge of its feature merge,
-// DESIGN 5.14).  Host side: rroi_host_plan.h (tuning table,
+// DESIGN 5.14), rroi_conv3x3_kernels.h (+ rroi_conv3x3_host.h: its dense 3x3 convolutions on the matrix cores, bfloat16 /
+// float16).  Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
 // launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
 #include <hip/hip_runtime.h>
@@ -62,6 +63,7 @@ namespace {
 #include "rroi_instancenorm_kernels.h"
 #include "rroi_heads_kernels.h"
 #include "rroi_merge_kernels.h"
+#include "rroi_conv3x3_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
@@ -70,6 +72,7 @@ namespace {
 #include "rroi_instancenorm_host.h"
 #include "rroi_heads_host.h"
 #include "rroi_merge_host.h"
+#include "rroi_conv3x3_host.h"
 
 }  // namespace
 
@@ -740,6 +743,57 @@ int rroi_merge_forward_forced_hip(int dtype, const void* a, int a_h, int a_w, co
     if (v_used) *v_used = P.V;
     if (k_used) *k_used = P.K;
     return merge_impl(P, dtype, a, gate, f, y, channels, width, stream);
+}
+#endif
+
+// ------------------------------------------------------------------------------------
+// Dense 3x3 convolution on the matrix cores, bfloat16 / float16 (header section 9): one launch, no workspace.
+// ------------------------------------------------------------------------------------
+int rroi_conv3x3_plan(int dtype, int batch_size, int in_channels, int out_channels, int height, int width, int stride,
+                      rroi_conv3x3_plan_info* plan)
+{
+    const ConvPlan P = plan_conv3x3(dtype, batch_size, in_channels, out_channels, height, width, stride);
+    if (!P.status || !plan) return 0;
+    *plan = rroi_conv3x3_plan_info{32 * P.MT, 4 * P.NT, kCvTileW, P.KC, (int)P.k_chunks, (int)P.m_tiles, (int)P.y_tiles,
+                                   (int)P.x_tiles, (int)P.grid, kCvThreads, P.lds_bytes, P.Ho, P.Wo, 0};
+    return 1;
+}
+
+static int conv3x3_impl(const ConvPlan& P, int dtype, const void* x, const void* w, void* y, int in_channels, int out_channels,
+                        int height, int width, int stride, float negative_slope, void* stream_)
+{
+    if (!P.status) return 0;
+    if (!x || !w || !y) return 0;
+    if (!std::isfinite(negative_slope)) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (dtype == RROI_DTYPE_BF16)
+        return launch_conv3x3(P, static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(w), static_cast<bf16_t*>(y),
+                              (unsigned)in_channels, (unsigned)out_channels, (unsigned)height, (unsigned)width, stride,
+                              negative_slope, stream);
+    return launch_conv3x3(P, static_cast<const fp16_t*>(x), static_cast<const fp16_t*>(w), static_cast<fp16_t*>(y),
+                          (unsigned)in_channels, (unsigned)out_channels, (unsigned)height, (unsigned)width, stride,
+                          negative_slope, stream);
+}
+
+int rroi_conv3x3_forward_hip(int dtype, const void* x, const void* w, void* y, int batch_size, int in_channels,
+                             int out_channels, int height, int width, int stride, float negative_slope, void* stream)
+{
+    return conv3x3_impl(plan_conv3x3(dtype, batch_size, in_channels, out_channels, height, width, stride), dtype, x,
+                        w, y, in_channels, out_channels, height, width, stride, negative_slope, stream);
+}
+
+#ifdef RROI_CONV3X3_MEASURE
+// Measurement build only (`make conv-forms`; not declared in the header, not in the shipped library): the convolution with
+// the tile shape (32 * force_mt channels, 4 * force_nt rows) and the K chunk forced, for the comparison of the plan rule
+// against its neighbours (tools/conv3x3_bench.py --forms).  *used = {MT, NT, KC} that ran.
+int rroi_conv3x3_forward_forced_hip(int dtype, const void* x, const void* w, void* y, int batch_size, int in_channels,
+                                    int out_channels, int height, int width, int stride, float negative_slope, int force_mt,
+                                    int force_nt, int force_kc, int* used, void* stream)
+{
+    const ConvPlan P = plan_conv3x3(dtype, batch_size, in_channels, out_channels, height, width, stride, force_mt,
+                                    force_nt, force_kc);
+    if (used) used[0] = P.MT, used[1] = P.NT, used[2] = P.KC;
+    return conv3x3_impl(P, dtype, x, w, y, in_channels, out_channels, height, width, stride, negative_slope, stream);
 }
 #endif
 

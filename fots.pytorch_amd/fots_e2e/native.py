@@ -29,6 +29,12 @@ What `model.py` applies functionally around its norms -- the stem's `cat(x, -x)`
 pass, on the two largest tensors of the network), the ReLU behind `_PlainBlock.bn1`, and the shortcut add and activation
 of all 17 residual blocks -- is folded into the norm's own launch after `use_native_blocks(net)`:
 `rroi_align._ext.rroi_align.instance_norm_fused` wherever `fused_norm_ok` holds, the stock forward otherwise.
+
+The 23 dense 3x3 convolutions -- stem, `layer0_1`, `layer1`, `layer2`, the recogniser's `conv5` - `conv9` -- are the last
+large item on stock kernels.  In bfloat16 / float16 `use_native_conv3x3(net)` switches them to `DenseConv3x3`, which calls
+`rroi_align._ext.rroi_align.conv3x3` (an implicit GEMM on the matrix cores, one launch, the ReLU of
+`layer0_1` fused) wherever `conv3x3_ok` holds and `nn.Conv2d.forward` otherwise; float32 inputs always take the stock
+path, and so does every shape class `_conv3x3_slower` lists.
 """
 import torch
 import torch.nn as nn
@@ -429,3 +435,134 @@ def use_native_blocks(net: nn.Module, enable: bool = True):
                 counts[k] += 1
                 break
     return tuple(counts)
+
+
+# --------------------------------------------------------------------------- dense 3x3 convolutions, bf16 / fp16, DESIGN 5.15
+_CONV_DTYPES = (torch.bfloat16, torch.float16)
+
+
+def _dense_static_ok(m) -> bool:
+    """What of `conv3x3_ok` depends on the module alone: an exact 3x3, padding 1, stride 1 or 2, groups 1, no bias."""
+    return (m.kernel_size == (3, 3) and m.padding == (1, 1) and m.dilation == (1, 1) and m.stride in ((1, 1), (2, 2))
+            and m.groups == 1 and m._parameters["bias"] is None and m.padding_mode == "zeros")
+
+
+def conv3x3_ok(m, x) -> bool:
+    """True where `m(x)` may run the native matrix-core kernel: pure, no GPU needed to ask.  A 16-bit dtype equal to the
+    weight's (float32 keeps the stock Winograd kernels: DESIGN 5.15), a contiguous CUDA 4-D input of fewer than 2^31
+    elements whose output stays below that too, no autocast, no gradient needed, and not one of the shape classes that
+    measured slower (`_conv3x3_slower`)."""
+    w = m._parameters["weight"]
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype == w.dtype and x.dtype in _CONV_DTYPES
+            and x.is_contiguous() and _dense_static_ok(m) and x.size(1) == m.in_channels and w.device == x.device
+            and w.is_contiguous() and 0 < x.numel() < (1 << 31)):
+        return False
+    s = m.stride[0]
+    return (x.size(0) * m.out_channels * ((x.size(2) - 1) // s + 1) * ((x.size(3) - 1) // s + 1) < (1 << 31)
+            and not _conv3x3_slower(m, x)
+            and not torch.is_autocast_enabled()
+            and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)))
+
+
+def _conv3x3_slower(m, x) -> bool:
+    """The shape classes in which the native kernel's median was not below the stock one's (profiles/native_conv3x3.md,
+    microseconds per call, native / stock, bf16 | fp16).  With M = N * Cout * Ho * Wo * 9 * Cin multiply-adds:
+      stride 1, M above 5.0e9 (bf16) / 2.5e9 (fp16): the kernel reaches 130-190 TFLOP/s where MIOpen's reach up to 470 --
+        64>64 at 352x640 (M 8.3e9) 98/83 | 98/83; 256>256 on 24 crops (6.8e9) 106/81 | 106/52; every row of eight images
+        or 192 crops, e.g. 128>128 at 88x160 x 8 (16.6e9) 172/98 | 172/100.  Below the line it wins: 64>64 at 176x320 and
+        128>128 at 88x160 (2.1e9) 30/45 and 35/45 in both types, 64>128 on 24 crops (1.9e9) 24/59 | 23/45.  Between
+        2.5e9 and 5.0e9 the types part -- 128>128 and 128>256 on 24 crops (3.7e9, 3.4e9): 56/83 and 45/75 in bf16, where
+        the stock path has no Winograd kernel, 56/52 and 45.4/44.8 in fp16; the lines are drawn between the nearest
+        measured rows on either side.
+      stride 2, except Cout <= 32 with M <= 2.5e9: the input tile with its halo is four times the output tile, and the
+        staging dominates -- 64>128 at 176x320 (1.0e9) 56/45 | 56/45, 64>64 at 352x640 (2.1e9) 59/54 | 59/50, 32>32 at
+        704x1280 x 8 (16.6e9) 584/461 | 583/395; the stem's 32>32 at one image (2.1e9) wins 64/69 | 64.2/64.8.
+    Fewer than 16 input channels (the stem's 3>16) win at every measured size, 27/62 at one image and 186/375 at eight."""
+    if m.in_channels < 16:
+        return False
+    s = m.stride[0]
+    macs = x.size(0) * m.out_channels * ((x.size(2) - 1) // s + 1) * ((x.size(3) - 1) // s + 1) * 9 * m.in_channels
+    if s == 2:
+        return not (m.out_channels <= 32 and macs <= 2.5e9)
+    return macs > (5.0e9 if x.dtype == torch.bfloat16 else 2.5e9)
+
+
+class DenseConv3x3(nn.Conv2d):
+    """An `nn.Conv2d` (same parameters, same `state_dict` keys) whose forward runs the native matrix-core kernel where
+    `conv3x3_ok(self, x)` holds.  `fused_slope` (None: nothing absorbed) is the negative slope of an activation that
+    `use_native_conv3x3` has folded into this module: it is applied on BOTH paths, so the pair computes the same function
+    whichever path a call takes."""
+    fused_slope = None
+
+    def forward(self, x):
+        slope = self.fused_slope
+        if conv3x3_ok(self, x):
+            return _ext()._conv3x3_run(x, self._parameters["weight"], self.stride[0], 1.0 if slope is None else slope)
+        y = super().forward(x)
+        if slope is None:
+            return y
+        return F.relu(y) if slope == 0.0 else F.leaky_relu(y, slope)
+
+
+class ConvAppliedLeakyReLU(nn.LeakyReLU):
+    """An `nn.LeakyReLU` whose work the `DenseConv3x3` in front of it does: returns its input.  (A class of this switch's
+    own: `use_native_instancenorm(net, enable=False)` restores every `Absorbed*` and must not re-arm this one.)"""
+
+    def forward(self, x):
+        return x
+
+
+class ConvAppliedReLU(nn.ReLU):
+    """An `nn.ReLU` whose work the `DenseConv3x3` in front of it does: returns its input."""
+
+    def forward(self, x):
+        return x
+
+
+_CONV_APPLIED = {nn.LeakyReLU: ConvAppliedLeakyReLU, nn.ReLU: ConvAppliedReLU}
+
+
+def use_native_conv3x3(net: nn.Module, enable: bool = True, fuse_activation: bool = True):
+    """Switch every qualifying `nn.Conv2d` of `net` -- by exact type: a dense 3x3, padding 1, stride 1 or 2, no bias -- to
+    `DenseConv3x3` (23 for `FOTSNet()`: 18 in the trunk, conv5 - conv9), and -- with `fuse_activation` -- let every
+    switched convolution that an `nn.Sequential` follows directly with an `nn.ReLU` / `nn.LeakyReLU` take over that
+    activation's slope, the activation becoming a pass-through (the two pairs of `layer0_1` for `FOTSNet()`).  A pair is
+    fused only where both modules occur once in `net`.  enable=False: every class back, every slope removed.  Only
+    classes change: no parameter is copied, no key of the state_dict moves; the pass-through classes are this switch's
+    own, so it and `use_native_instancenorm` leave each other's work alone in either order.  Whether a call runs the
+    native kernel is decided per call by `conv3x3_ok` (float32 never does).  Returns (convolutions switched, activations
+    absorbed)."""
+    convs = acts = 0
+    if not enable:
+        for m in net.modules():
+            if type(m) is DenseConv3x3:
+                m.__dict__.pop("fused_slope", None)
+                m.__class__ = nn.Conv2d
+                convs += 1
+            else:
+                for stock, applied in _CONV_APPLIED.items():
+                    if type(m) is applied:
+                        m.__class__ = stock
+                        acts += 1
+        return convs, acts
+    for m in net.modules():
+        if type(m) is nn.Conv2d and _dense_static_ok(m):
+            m.__class__ = DenseConv3x3
+            convs += 1
+    if fuse_activation:
+        uses = {}
+        for m in net.modules():
+            for child in m._modules.values():
+                if child is not None:
+                    uses[id(child)] = uses.get(id(child), 0) + 1
+        for seq in net.modules():
+            if not isinstance(seq, nn.Sequential):
+                continue
+            mods = list(seq._modules.values())
+            for conv, act in zip(mods, mods[1:]):
+                if (type(conv) is DenseConv3x3 and conv.fused_slope is None and type(act) in _CONV_APPLIED
+                        and uses[id(conv)] == 1 and uses[id(act)] == 1):
+                    conv.fused_slope = float(getattr(act, "negative_slope", 0.0))
+                    act.__class__ = _CONV_APPLIED[type(act)]
+                    acts += 1
+    return convs, acts

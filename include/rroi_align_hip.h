@@ -684,6 +684,47 @@ int rroi_merge_forward_hip(int dtype, const void* a, int a_h, int a_w, const voi
 int rroi_merge_plan(int dtype, int batch_size, int channels, int height, int width, int a_h, int a_w, int g_h, int g_w,
                     int gated, rroi_merge_plan_info* plan);
 
+/* ------------------------------------------------------------------------- *
+ * 9. The network's dense 3x3 convolution on the matrix cores, bfloat16 / float16:
+ *    y = act(conv2d(x, w, stride, padding = 1)) in ONE launch.  Forward only; opt-in from Python
+ *    (fots_e2e.native.use_native_conv3x3).
+ *
+ *      x   (N, Cin, H, W)      w   (Cout, Cin, 3, 3)      y   (N, Cout, Ho, Wo),  Ho = (H - 1) / stride + 1, Wo likewise
+ *    all contiguous NCHW of one 16-bit element type `dtype` (RROI_DTYPE_BF16 / RROI_DTYPE_FP16); stride 1 or 2; no bias,
+ *    groups 1, dilation 1; any Cin >= 1 and Cout >= 1.  act(v) = v < 0 ? v * negative_slope : v in fp32: 1.0 is no
+ *    activation, 0.0 a ReLU.  Every element of y is written and nothing else is; nothing outside x is read (the padding
+ *    is a zero fill inside the kernel); y may overlap no input.  Any element-aligned x, w and y work.
+ *
+ *    Arithmetic: an implicit GEMM on v_mfma_f32_32x32x16_{bf16,f16} with fp32 accumulators; products of two 16-bit values
+ *    are exact in fp32; K = (tap, cin) is summed in an order the plan fixes (no atomic, no split of K across workgroups),
+ *    so repeated calls give the same bits; ONE rounding from fp32 to the tensor's type, after the activation.  Not
+ *    bit-exact against another summation order: with ref the exact convolution and S that of |x| with |w|,
+ *    |y - act(ref)| <= 9 Cin 2^-23 S + u |act(ref)| (+ 2^-25 in fp16's subnormal range), u = 2^-8 (bf16) / 2^-11 (fp16).
+ *
+ *    Returns 1 / 0 / -hipError.  0, before any launch: fp32 or an unknown dtype, a dimension below 1, a stride other than
+ *    1 or 2, x, w or y of 2^31 elements or more, a NULL x, w or y, a non-finite negative_slope.  Each call enqueues one
+ *    kernel on `stream`, uses no workspace, allocates nothing and can be captured into a HIP graph.  Arrived after 0.10.0
+ *    under the same version string: detect it by symbol.
+ * ------------------------------------------------------------------------- */
+typedef struct rroi_conv3x3_plan_info {
+    int tile_m;      /* output channels per workgroup: 32 */
+    int tile_h;      /* output rows per workgroup: 4 (one per wave) */
+    int tile_w;      /* output columns per workgroup: 32 */
+    int k_chunk;     /* input channels staged through LDS at a time: 16 */
+    int k_chunks;    /* ceil(Cin / k_chunk) */
+    int m_tiles, y_tiles, x_tiles;   /* tiles per image along Cout, Ho and Wo */
+    int grid_x;      /* workgroups: N * m_tiles * y_tiles * x_tiles */
+    int block;       /* threads per workgroup: 256 */
+    int lds_bytes;   /* the input tile with its halo + the chunk's weights */
+    int out_h, out_w;
+    int reserved;
+} rroi_conv3x3_plan_info;
+int rroi_conv3x3_forward_hip(int dtype, const void* x, const void* w, void* y, int batch_size, int in_channels,
+                             int out_channels, int height, int width, int stride, float negative_slope, void* stream);
+/* host only, no launch; 1, or 0 for arguments the call would refuse */
+int rroi_conv3x3_plan(int dtype, int batch_size, int in_channels, int out_channels, int height, int width, int stride,
+                      rroi_conv3x3_plan_info* plan);
+
 /* Bin centres only: geom (R, PH, PW, 2) = (bin_cx, bin_cy), 0 where the bin is
  * outside the ROI's pooled width (kernel.cu:86-107).  Diagnostic / test hook. */
 int rroi_align_bin_centres_hip(float spatial_scale, int num_rois, int height, int width,
@@ -714,8 +755,8 @@ int rroi_align_get_trig_recipe_hip(void);
 /* Identification: "rroi_align_hip <version> gfx950" (0.7.0: per-call trig recipe, device-wide setter removed; 0.8.0: launcher scratch reused within a capture, table of 64, stats; 0.9.0: plan query; 0.10.0: bfloat16 / float16 tensors).
  * The typed callers' entry points (rroi_rbox_decode_typed_hip, rroi_ctc_greedy_decode_typed_hip) arrived after 0.10.0 under
  * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b, the depthwise
- * convolution of section 5, the InstanceNorm of section 6, its fused epilogues of section 6b, the heads and gate of section 7 and the gated merge
- * of section 8. */
+ * convolution of section 5, the InstanceNorm of section 6, its fused epilogues of section 6b, the heads and gate of section 7, the gated merge
+ * of section 8 and the dense 3x3 convolution of section 9. */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
