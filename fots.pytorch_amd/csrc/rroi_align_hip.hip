@@ -30,7 +30,8 @@
 // InstanceNorm2d with the activation behind it), rroi_heads_kernels.h (+ rroi_heads_host.h: its detection heads
 // and attention gate), rroi_merge_kernels.h (+ rroi_merge_host.h: the gated merge of its feature merge,
 // DESIGN 5.14), rroi_conv3x3_kernels.h (+ rroi_conv3x3_host.h: its dense 3x3 convolutions on the matrix cores, bfloat16 /
-// float16).  Host side: rroi_host_plan.h (tuning table,
+// float16), rroi_recogniser_kernels.h (+ rroi_recogniser_host.h: the recogniser's log-softmax head and its
+// activation + (2,1) max-pool).  Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
 // launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
 #include <hip/hip_runtime.h>
@@ -64,6 +65,7 @@ namespace {
 #include "rroi_heads_kernels.h"
 #include "rroi_merge_kernels.h"
 #include "rroi_conv3x3_kernels.h"
+#include "rroi_recogniser_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
@@ -73,6 +75,7 @@ namespace {
 #include "rroi_heads_host.h"
 #include "rroi_merge_host.h"
 #include "rroi_conv3x3_host.h"
+#include "rroi_recogniser_host.h"
 
 }  // namespace
 
@@ -796,6 +799,47 @@ int rroi_conv3x3_forward_forced_hip(int dtype, const void* x, const void* w, voi
     return conv3x3_impl(P, dtype, x, w, y, in_channels, out_channels, height, width, stride, negative_slope, stream);
 }
 #endif
+
+// ------------------------------------------------------------------------------------
+// The recogniser's head and its activation + (2,1) max-pool (header section 10): one launch each, no workspace.
+// ------------------------------------------------------------------------------------
+int rroi_ocr_head_plan(int dtype, int batch_size, int channels, int classes, int steps, rroi_ocr_head_plan_info* plan)
+{
+    const OcrHeadPlan P = plan_ocr_head(dtype, batch_size, channels, classes, steps);
+    if (!P.status || !plan) return 0;
+    *plan = rroi_ocr_head_plan_info{kOhClasses, P.S, kOhCols, (int)P.tiles, (int)P.grid, P.S * 64, (int)P.lds_bytes,
+                                    kOhMaxClasses};
+    return 1;
+}
+
+int rroi_ocr_head_forward_hip(int dtype, const void* x, const void* w, const void* b, void* y, int batch_size, int channels,
+                              int classes, int steps, void* stream_)
+{
+    const OcrHeadPlan P = plan_ocr_head(dtype, batch_size, channels, classes, steps);
+    if (!P.status) return 0;
+    if (!x || !w || !y) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_ocr_head(P, static_cast<const T*>(x), static_cast<const T*>(w), static_cast<const T*>(b),
+                               static_cast<T*>(y), (unsigned)channels, (unsigned)classes, (unsigned)steps, stream);
+    });
+}
+
+int rroi_act_maxpool2x1_forward_hip(int dtype, const void* x, void* y, int batch_size, int channels, int height, int width,
+                                    float negative_slope, void* stream_)
+{
+    const ActPoolPlan P = plan_act_pool(dtype, batch_size, channels, height, width);
+    if (!P.status) return 0;
+    if (!x || !y) return 0;
+    if (!std::isfinite(negative_slope)) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_act_pool(P, static_cast<const T*>(x), static_cast<T*>(y), (unsigned)height, (unsigned)width,
+                               negative_slope, stream);
+    });
+}
 
 int rroi_align_set_trig_recipe_hip(int recipe) { return recipe == RROI_TRIG_DOUBLE ? 1 : 0; }   // deprecated shim, see the header
 int rroi_align_get_trig_recipe_hip(void) { return RROI_TRIG_DOUBLE; }

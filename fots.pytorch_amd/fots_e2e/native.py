@@ -35,6 +35,14 @@ large item on stock kernels.  In bfloat16 / float16 `use_native_conv3x3(net)` sw
 `rroi_align._ext.rroi_align.conv3x3` (an implicit GEMM on the matrix cores, one launch, the ReLU of
 `layer0_1` fused) wherever `conv3x3_ok` holds and `nn.Conv2d.forward` otherwise; float32 inputs always take the stock
 path, and so does every shape class `_conv3x3_slower` lists.
+
+The recogniser, `FOTSNet.forward_ocr`, runs once per pooled-width bucket, several times per image, and half of its launches
+do no arithmetic worth one: nine functional LeakyReLUs, and a bias add and a log-softmax behind `conv11`.  After
+`use_native_recogniser(net)` every activation is folded into the native call in front of it (`_conv3x3_run`,
+`_instance_norm_run`) or behind it (`rroi_align._ext.rroi_align.act_maxpool2x1`: LeakyReLU + (2,1) max-pool), and the tail
+-- `conv11`, its bias, the log-softmax -- is one launch, `rroi_align._ext.rroi_align.ocr_head`, each step
+where its own predicate holds (`fused_norm_ok`, `conv3x3_ok`, `act_pool_ok`, `ocr_head_ok`) and the stock expression
+otherwise.  `conv10_s` stays stock.
 """
 import torch
 import torch.nn as nn
@@ -262,10 +270,13 @@ def _switch_class(net, pairs, enable) -> bool:
 
 def use_native_heads(net: nn.Module, enable: bool = True) -> bool:
     """Switch a network whose type is exactly `FOTSNet` to `NativeHeadsFOTSNet` (enable=False: back), and one that
-    `use_native_merge` has switched, `NativeMergeFOTSNet`, to `NativeHeadsMergeFOTSNet`.  Only the class of the network
-    changes: no parameter is copied, no key of the state_dict moves; the module switches above and `use_native_merge`
-    compose with it in any order.  A network of any other type is left alone.  Returns whether the class was switched."""
-    return _switch_class(net, ((FOTSNet, NativeHeadsFOTSNet), (NativeMergeFOTSNet, NativeHeadsMergeFOTSNet)), enable)
+    `use_native_merge` has switched, `NativeMergeFOTSNet`, to `NativeHeadsMergeFOTSNet`; likewise the two types that
+    `use_native_recogniser` makes of those.  Only the class of the network changes: no parameter is copied, no key of the
+    state_dict moves; the module switches above, `use_native_merge` and `use_native_recogniser` compose with it in any
+    order.  A network of any other type is left alone.  Returns whether the class was switched."""
+    return _switch_class(net, ((FOTSNet, NativeHeadsFOTSNet), (NativeMergeFOTSNet, NativeHeadsMergeFOTSNet),
+                               (NativeRecogniserFOTSNet, NativeHeadsRecogniserFOTSNet),
+                               (NativeMergeRecogniserFOTSNet, NativeHeadsMergeRecogniserFOTSNet)), enable)
 
 
 # --------------------------------------------------------------------------- the feature merge, DESIGN 5.14
@@ -328,10 +339,13 @@ class NativeHeadsMergeFOTSNet(_NativeMerge, NativeHeadsFOTSNet):
 
 def use_native_merge(net: nn.Module, enable: bool = True) -> bool:
     """Switch a network whose type is exactly `FOTSNet` to `NativeMergeFOTSNet`, or exactly `NativeHeadsFOTSNet` to
-    `NativeHeadsMergeFOTSNet` (enable=False: back).  Only the class of the network changes: no parameter is copied, no key
-    of the state_dict moves; it composes with `use_native_heads` and the module switches in any order.  A network of any
-    other type is left alone.  Returns whether the class was switched."""
-    return _switch_class(net, ((FOTSNet, NativeMergeFOTSNet), (NativeHeadsFOTSNet, NativeHeadsMergeFOTSNet)), enable)
+    `NativeHeadsMergeFOTSNet` (enable=False: back); likewise the two types that `use_native_recogniser` makes of those.
+    Only the class of the network changes: no parameter is copied, no key of the state_dict moves; it composes with
+    `use_native_heads`, `use_native_recogniser` and the module switches in any order.  A network of any other type is
+    left alone.  Returns whether the class was switched."""
+    return _switch_class(net, ((FOTSNet, NativeMergeFOTSNet), (NativeHeadsFOTSNet, NativeHeadsMergeFOTSNet),
+                               (NativeRecogniserFOTSNet, NativeMergeRecogniserFOTSNet),
+                               (NativeHeadsRecogniserFOTSNet, NativeHeadsMergeRecogniserFOTSNet)), enable)
 
 
 # --------------------------------------------------------------------------- the stem's mirror and the blocks' tails, DESIGN 5.13
@@ -566,3 +580,135 @@ def use_native_conv3x3(net: nn.Module, enable: bool = True, fuse_activation: boo
                     act.__class__ = _CONV_APPLIED[type(act)]
                     acts += 1
     return convs, acts
+
+
+# --------------------------------------------------------------------------- the recogniser, DESIGN 5.16
+_OCR_HEAD_MAX_CLASSES = 128   # RROI_OCR_HEAD_MAX_CLASSES of the header (the binding's OCR_HEAD_MAX_CLASSES)
+
+
+def act_pool_ok(x, slope: float = 0.01) -> bool:
+    """True where `F.max_pool2d(F.leaky_relu(x, slope), (2, 1), stride=(2, 1))` (slope 1.0: the pool alone) may run the
+    native kernel: pure, no GPU needed to ask.  A contiguous CUDA 4-D tensor of one of the three dtypes with at least two
+    rows and fewer than 2^31 elements, no autocast, no gradient needed, and not a class of `_act_pool_slower`."""
+    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype in _DTYPES and x.is_contiguous()
+            and x.size(2) >= 2 and 0 < x.numel() < (1 << 31) and not _act_pool_slower(x, slope)
+            and not torch.is_autocast_enabled()
+            and not (torch.is_grad_enabled() and x.requires_grad))
+
+
+def _act_pool_slower(x, slope: float = 0.01) -> bool:
+    """The shape classes in which the native kernel's median was not below the stock one's
+    (profiles/native_recogniser.md, microseconds per call, native / stock; the three dtypes agree to about 1 us).
+      With an activation to apply (slope != 1.0), against the stock pair: none -- all 54 rows win, 9.3 / 11.4 on 8 crops of
+        32 columns up to 16.5 / 104.9 (bf16) and 27.4 / 134.7 (fp32) on 192 crops of 128.
+      The pool alone (slope 1.0), against `F.max_pool2d` alone, where no launch is saved: below 3.0e6 elements -- both
+        calls are then bound by what the host can issue, 8.8 - 9.4 for the call through ctypes against 5.5 - 8.1: every row
+        of 8 crops (9.4 / 6.2), 24 crops of 32 columns (9.4 / 6.1) and of 64 (128 x 11 rows, 2.2e6 elements: 9.4 / 8.1;
+        256 x 5 rows, 2.0e6: 9.3 / 6.9).  From 24 crops of 128 (3.9e6 and 4.3e6 elements) it wins, 9.5 / 11.4 and
+        9.4 / 13.7, up to 16.5 / 81.8 on 192 crops of 128 (bf16); the line is drawn between the nearest measured rows,
+        2.2e6 and 3.9e6 elements.  30 of 54 rows lose, 24 win."""
+    return slope == 1.0 and x.numel() < 3.0e6
+
+
+def ocr_head_ok(net, x) -> bool:
+    """True where `F.log_softmax(net.conv11(x).squeeze(2), dim=1)` may run the native kernel: pure, no GPU needed to ask.
+    A contiguous CUDA (N, C, 1, T) tensor of one of the three dtypes, `conv11` a plain 1x1 convolution from C channels
+    with parameters of that dtype on that device and at most 128 classes, fewer than 2^31 elements in and out, no
+    autocast, no gradient needed, and not a class of `_ocr_head_slower`."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype in _DTYPES and x.is_contiguous()
+            and x.size(2) == 1 and 0 < x.numel() < (1 << 31)):
+        return False
+    m = net._modules.get("conv11")
+    return (type(m) is nn.Conv2d and 1 <= m.out_channels <= _OCR_HEAD_MAX_CLASSES
+            and _pointwise_conv_ok(m, m.out_channels, x) and m._parameters["weight"].is_contiguous()
+            and x.size(0) * m.out_channels * x.size(3) < (1 << 31) and not _ocr_head_slower(m, x)
+            and not torch.is_autocast_enabled()
+            and not (torch.is_grad_enabled() and x.requires_grad))
+
+
+def _ocr_head_slower(m, x) -> bool:
+    """The shape classes in which the native kernel's median was not below that of the stock convolution + log-softmax
+    (profiles/native_recogniser.md, 256 channels to 87 classes, microseconds per call, native / stock, fp32 | bf16 | fp16):
+    more than 4,608 columns N * T.  A workgroup takes 16 columns and runs for 29 us whatever the grid, so up to 192
+    workgroups the call takes 29 - 30 us -- 8 crops of 32 columns 28.9 / 42.7 | 29.5 / 41.7 | 29.8 / 41.6, 24 crops of 128
+    (3,072 columns) 29.4 / 56.0 | 29.9 / 54.9 | 30.2 / 56.0 -- and beyond that it grows with the grid where the stock GEMM
+    does not: 192 crops of 32 (6,144 columns) 43.0 / 43.0 | 44.6 / 41.7 | 44.1 / 41.7, of 128 117.7 / 68.6 | 122.9 / 60.4 |
+    122.8 / 60.6.  All 18 rows of 8 and 24 crops win, all 9 of 192 crops do not; the line is drawn between the nearest
+    measured rows, 3,072 and 6,144 columns."""
+    return x.size(0) * x.size(3) > 4608
+
+
+def _ocr_norm_act(norm, t):
+    """act(norm(t)): one native call where `fused_norm_ok` holds."""
+    if fused_norm_ok(norm, t):
+        return _ext()._instance_norm_run(t, *_affine(norm), norm.eps, 0.01)
+    return F.leaky_relu(norm(t), 0.01)
+
+
+def _ocr_conv_act(conv, t, before_pool: bool):
+    """act(conv(t)) -> (tensor, the slope the pool behind it still has to apply: 1.0 where the activation is done).  One
+    native call where `use_native_conv3x3` has switched the module, it carries no slope of its own and `conv3x3_ok`
+    holds; otherwise the module, and its activation either at once or -- in front of a pool -- left to the pool."""
+    if isinstance(conv, DenseConv3x3) and conv.fused_slope is None and conv3x3_ok(conv, t):
+        return _ext()._conv3x3_run(t, conv._parameters["weight"], conv.stride[0], 0.01), 1.0
+    y = conv(t)
+    return (y, 0.01) if before_pool else (F.leaky_relu(y, 0.01), 1.0)
+
+
+def _ocr_pool(t, slope: float):
+    """pool(act(t)), act of `slope` (1.0: already applied): one native call where `act_pool_ok` holds."""
+    if act_pool_ok(t, slope):
+        return _ext()._act_maxpool2x1_run(t, slope)
+    if slope != 1.0:
+        t = F.leaky_relu(t, slope)
+    return F.max_pool2d(t, (2, 1), stride=(2, 1))
+
+
+class _NativeRecogniser:
+    """Mixin in front of a `FOTSNet`: `forward_ocr` with every activation folded into the call in front of it or behind it
+    and the tail -- `conv11`, its bias, the log-softmax -- as one native call.  Each step asks its own predicate and runs
+    the stock expression where that fails; nothing is computed twice.  `conv10_s` and the first convolution (whose input
+    may be a non-contiguous crop view) stay on their modules.  A network in training mode takes the stock method."""
+
+    def forward_ocr(self, x):
+        if self.training:
+            return super().forward_ocr(x)
+        x = _ocr_norm_act(self.batch5, self.conv5(x))
+        x, _ = _ocr_conv_act(self.conv6, x, False)
+        x = _ocr_pool(*_ocr_conv_act(self.conv6, x, True))
+        x = _ocr_norm_act(self.batch7, self.conv7(x))
+        x, _ = _ocr_conv_act(self.conv8, x, False)
+        x, _ = _ocr_conv_act(self.conv8, x, False)
+        x, _ = _ocr_conv_act(self.conv9, x, False)
+        x = _ocr_pool(*_ocr_conv_act(self.conv9, x, True))
+        x = _ocr_norm_act(self.batch10_s, self.conv10_s(x))
+        if ocr_head_ok(self, x):
+            return _ext()._ocr_head_run(x, *_wb(self.conv11))
+        return F.log_softmax(self.conv11(self.drop1(x)).squeeze(2), dim=1)
+
+
+class NativeRecogniserFOTSNet(_NativeRecogniser, FOTSNet):
+    """A `FOTSNet` (same modules, same `state_dict` keys) whose `forward_ocr` runs the native head and pools."""
+
+
+class NativeHeadsRecogniserFOTSNet(_NativeRecogniser, NativeHeadsFOTSNet):
+    """A `NativeHeadsFOTSNet` with the native recogniser."""
+
+
+class NativeMergeRecogniserFOTSNet(_NativeRecogniser, NativeMergeFOTSNet):
+    """A `NativeMergeFOTSNet` with the native recogniser."""
+
+
+class NativeHeadsMergeRecogniserFOTSNet(_NativeRecogniser, NativeHeadsMergeFOTSNet):
+    """A `NativeHeadsMergeFOTSNet` with the native recogniser."""
+
+
+def use_native_recogniser(net: nn.Module, enable: bool = True) -> bool:
+    """Switch a network whose type is exactly `FOTSNet`, `NativeHeadsFOTSNet`, `NativeMergeFOTSNet` or
+    `NativeHeadsMergeFOTSNet` to the subclass of it with the native `forward_ocr` (enable=False: back to exactly that
+    type).  Only the class of the network changes: no parameter is copied, no key of the state_dict moves; it composes with
+    `use_native_heads`, `use_native_merge` and the module switches in any order.  A network of any other type is left
+    alone.  Returns whether the class was switched."""
+    return _switch_class(net, ((FOTSNet, NativeRecogniserFOTSNet), (NativeHeadsFOTSNet, NativeHeadsRecogniserFOTSNet),
+                               (NativeMergeFOTSNet, NativeMergeRecogniserFOTSNet),
+                               (NativeHeadsMergeFOTSNet, NativeHeadsMergeRecogniserFOTSNet)), enable)

@@ -725,6 +725,60 @@ int rroi_conv3x3_forward_hip(int dtype, const void* x, const void* w, void* y, i
 int rroi_conv3x3_plan(int dtype, int batch_size, int in_channels, int out_channels, int height, int width, int stride,
                       rroi_conv3x3_plan_info* plan);
 
+/* ------------------------------------------------------------------------- *
+ * 10. The recogniser's tail and pools, two kernels of one launch each.  Forward only; opt-in from Python
+ *    (fots_e2e.native.use_native_recogniser).
+ *
+ *    A. The head -- `log_softmax(conv11(x).squeeze(2), dim=1)` of tools/models.py: a 1x1 convolution with bias to the K
+ *    classes and the log-softmax over them, reading x once and writing y once.
+ *
+ *      x   (N, C, T)   the contiguous (N, C, 1, T) map      w   (K, C)      b   (K) or NULL (+0.0)      y   (N, K, T)
+ *    all contiguous, of one element type `dtype` (RROI_DTYPE_*); any C >= 1 and T >= 1; 1 <= K <=
+ *    RROI_OCR_HEAD_MAX_CLASSES.  Every element of y is written and nothing else is; y may overlap no input.
+ *
+ *    Arithmetic per column (n, t), the recipe of section 7, fixed so that two identical calls give identical bits:
+ *      every element of x, w and b is widened exactly to double where it is loaded
+ *      z_k = ((b_k + w[k][0] x[0]) + w[k][1] x[1]) + ...   in channel order; every product is exact in double
+ *      m = max_j z_j;   s = ((0 + exp(z_0 - m)) + exp(z_1 - m)) + ...   in class order;   L = m + log(s)
+ *      out = (T)(float)(z_k - L)
+ *    -- every operation rounded once in double (no contraction), one rounding to fp32 and one plain conversion to the
+ *    tensor's type (nearest even, NaN kept).  The logits are never rounded to 16 bits.  A NaN or +inf logit, or a column
+ *    whose logits are all -inf, makes that column's K outputs NaN; a -inf logit beside finite ones gives -inf in its own
+ *    class alone; no other column is affected.  A zero weight times an inf is NaN (no channel is skipped).  The order
+ *    depends on nothing but (C, K): not on the plan, an address or the device.
+ *    Any element-aligned x, w, b and y work.
+ *
+ *    B. Activation + (2,1) max-pool -- `F.max_pool2d(F.leaky_relu(x, s), (2, 1), stride=(2, 1))`, bit for bit:
+ *      x   (N, C, H, W)      y   (N, C, H / 2, W)     contiguous NCHW of one element type; H >= 2; an odd last row is dropped
+ *      a = (T)act((float)x[2i][j]),  c = (T)act((float)x[2i + 1][j]),  act(v) = v < 0 ? v * negative_slope : v  (fp32);
+ *      y[i][j] = c where c > a or c is a NaN, a otherwise: a NaN in either element gives NaN, a tie (signed zeros
+ *      included) keeps the upper row's element.  negative_slope = 1.0 is the plain pool.
+ *    Every element of y is written and nothing else is; y may not overlap x.  Any element-aligned x and y work.
+ *
+ *    Both return 1 / 0 / -hipError.  0, before any launch: an unknown dtype, a dimension below 1 (B: H below 2), K above
+ *    RROI_OCR_HEAD_MAX_CLASSES, x, w or y of 2^31 elements or more, a NULL x, w or y, (B) a non-finite negative_slope.
+ *    Each call enqueues one kernel on `stream`, uses no workspace, no atomics and no cache of repacked parameters,
+ *    allocates nothing and can be captured into a HIP graph.  Arrived after 0.10.0 under the same version string: detect
+ *    it by symbol.
+ * ------------------------------------------------------------------------- */
+#define RROI_OCR_HEAD_MAX_CLASSES 128
+typedef struct rroi_ocr_head_plan_info {
+    int class_block;     /* classes per wave: 32 (8 per row of 16 lanes) */
+    int waves;           /* S: waves per workgroup, ceil(K / class_block) */
+    int tile_columns;    /* columns per workgroup: 16 */
+    int tiles;           /* tiles per crop: ceil(T / tile_columns) */
+    int grid_x;          /* workgroups: N * tiles */
+    int block;           /* threads per workgroup: 64 * S */
+    int lds_bytes;       /* max(64 S, 16 K) doubles */
+    int max_classes;     /* RROI_OCR_HEAD_MAX_CLASSES */
+} rroi_ocr_head_plan_info;
+int rroi_ocr_head_forward_hip(int dtype, const void* x, const void* w, const void* b, void* y, int batch_size, int channels,
+                              int classes, int steps, void* stream);
+/* host only, no launch; 1, or 0 for arguments the call would refuse */
+int rroi_ocr_head_plan(int dtype, int batch_size, int channels, int classes, int steps, rroi_ocr_head_plan_info* plan);
+int rroi_act_maxpool2x1_forward_hip(int dtype, const void* x, void* y, int batch_size, int channels, int height, int width,
+                                    float negative_slope, void* stream);
+
 /* Bin centres only: geom (R, PH, PW, 2) = (bin_cx, bin_cy), 0 where the bin is
  * outside the ROI's pooled width (kernel.cu:86-107).  Diagnostic / test hook. */
 int rroi_align_bin_centres_hip(float spatial_scale, int num_rois, int height, int width,
@@ -756,7 +810,7 @@ int rroi_align_get_trig_recipe_hip(void);
  * The typed callers' entry points (rroi_rbox_decode_typed_hip, rroi_ctc_greedy_decode_typed_hip) arrived after 0.10.0 under
  * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b, the depthwise
  * convolution of section 5, the InstanceNorm of section 6, its fused epilogues of section 6b, the heads and gate of section 7, the gated merge
- * of section 8 and the dense 3x3 convolution of section 9. */
+ * of section 8, the dense 3x3 convolution of section 9 and the recogniser's head and activation + pool of section 10. */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
