@@ -31,7 +31,8 @@
 // and attention gate), rroi_merge_kernels.h (+ rroi_merge_host.h: the gated merge of its feature merge,
 // DESIGN 5.14), rroi_conv3x3_kernels.h (+ rroi_conv3x3_host.h: its dense 3x3 convolutions on the matrix cores, bfloat16 /
 // float16), rroi_recogniser_kernels.h (+ rroi_recogniser_host.h: the recogniser's log-softmax head and its
-// activation + (2,1) max-pool).  Host side: rroi_host_plan.h (tuning table,
+// activation + (2,1) max-pool), rroi_conv1x1_kernels.h (+ rroi_conv1x1_host.h: its bias-free 1x1 convolutions on
+// the matrix cores with the shortcut's BatchNorm folded in, bfloat16 / float16).  Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
 // launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
 #include <hip/hip_runtime.h>
@@ -66,6 +67,7 @@ namespace {
 #include "rroi_merge_kernels.h"
 #include "rroi_conv3x3_kernels.h"
 #include "rroi_recogniser_kernels.h"
+#include "rroi_conv1x1_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
@@ -76,6 +78,7 @@ namespace {
 #include "rroi_merge_host.h"
 #include "rroi_conv3x3_host.h"
 #include "rroi_recogniser_host.h"
+#include "rroi_conv1x1_host.h"
 
 }  // namespace
 
@@ -840,6 +843,66 @@ int rroi_act_maxpool2x1_forward_hip(int dtype, const void* x, void* y, int batch
                                negative_slope, stream);
     });
 }
+
+// ------------------------------------------------------------------------------------
+// 1x1 convolution on the matrix cores with an optional folded BatchNorm, bfloat16 / float16 (header section 11):
+// one launch, no workspace, no cache of folded parameters.
+// ------------------------------------------------------------------------------------
+int rroi_conv1x1_plan(int dtype, int batch_size, int in_channels, int out_channels, int height, int width, int stride,
+                      rroi_conv1x1_plan_info* plan)
+{
+    const Conv1x1Plan P = plan_conv1x1(dtype, batch_size, in_channels, out_channels, height, width, stride);
+    if (!P.status || !plan) return 0;
+    *plan = rroi_conv1x1_plan_info{32 * P.MT, kC1Pixels, kC1Chunk, (int)P.k_chunks, (int)P.m_tiles, (int)P.p_tiles,
+                                   (int)P.grid, kC1Threads, P.lds_bytes, P.Ho, P.Wo, 0};
+    return 1;
+}
+
+static int conv1x1_impl(const Conv1x1Plan& P, int dtype, const void* x, const void* w, void* y, int in_channels,
+                        int out_channels, int height, int width, int stride, float negative_slope, const void* bn_weight,
+                        const void* bn_bias, const void* bn_mean, const void* bn_var, double eps, void* stream_)
+{
+    if (!P.status) return 0;
+    if (!x || !w || !y) return 0;
+    if (!std::isfinite(negative_slope) || !std::isfinite(eps) || eps < 0.0) return 0;
+    if ((bn_weight == nullptr) != (bn_bias == nullptr) || (bn_mean == nullptr) != (bn_var == nullptr)) return 0;
+    if (bn_weight && !bn_mean) return 0;     // an affine pair without statistics is no norm
+    const Conv1x1Norm bn{bn_weight, bn_bias, bn_mean, bn_var, (float)eps};
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (dtype == RROI_DTYPE_BF16)
+        return launch_conv1x1(P, static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(w), static_cast<bf16_t*>(y), bn,
+                              (unsigned)in_channels, (unsigned)out_channels, (unsigned)height, (unsigned)width, stride,
+                              negative_slope, stream);
+    return launch_conv1x1(P, static_cast<const fp16_t*>(x), static_cast<const fp16_t*>(w), static_cast<fp16_t*>(y), bn,
+                          (unsigned)in_channels, (unsigned)out_channels, (unsigned)height, (unsigned)width, stride,
+                          negative_slope, stream);
+}
+
+int rroi_conv1x1_forward_hip(int dtype, const void* x, const void* w, void* y, int batch_size, int in_channels,
+                             int out_channels, int height, int width, int stride, float negative_slope,
+                             const void* bn_weight, const void* bn_bias, const void* bn_mean, const void* bn_var, double eps,
+                             void* stream)
+{
+    return conv1x1_impl(plan_conv1x1(dtype, batch_size, in_channels, out_channels, height, width, stride), dtype, x, w, y,
+                        in_channels, out_channels, height, width, stride, negative_slope, bn_weight, bn_bias, bn_mean, bn_var,
+                        eps, stream);
+}
+
+#ifdef RROI_CONV1X1_MEASURE
+// Measurement build only (`make conv1x1-forms`; not declared in the header, not in the shipped library): the convolution
+// with 32 * force_mt output channels per workgroup, for the comparison of the plan rule against its neighbour
+// (tools/conv1x1_bench.py --forms).  *mt_used = the MT that ran.
+int rroi_conv1x1_forward_forced_hip(int dtype, const void* x, const void* w, void* y, int batch_size, int in_channels,
+                                    int out_channels, int height, int width, int stride, float negative_slope,
+                                    const void* bn_weight, const void* bn_bias, const void* bn_mean, const void* bn_var,
+                                    double eps, int force_mt, int* mt_used, void* stream)
+{
+    const Conv1x1Plan P = plan_conv1x1(dtype, batch_size, in_channels, out_channels, height, width, stride, force_mt);
+    if (mt_used) *mt_used = P.MT;
+    return conv1x1_impl(P, dtype, x, w, y, in_channels, out_channels, height, width, stride, negative_slope, bn_weight,
+                        bn_bias, bn_mean, bn_var, eps, stream);
+}
+#endif
 
 int rroi_align_set_trig_recipe_hip(int recipe) { return recipe == RROI_TRIG_DOUBLE ? 1 : 0; }   // deprecated shim, see the header
 int rroi_align_get_trig_recipe_hip(void) { return RROI_TRIG_DOUBLE; }

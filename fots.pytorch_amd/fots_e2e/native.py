@@ -1,6 +1,7 @@
 """fots_e2e.native -- the operators of FOTSNet that run on the package's own kernels: its depthwise 3x3 convolutions, its
 InstanceNorms (with the activation behind them, the stem's mirror in front of them and the residual add of a block's tail),
-its detection heads and attention gates, and the gated merges of its feature merge.
+its detection heads and attention gates, the gated merges of its feature merge, its dense 3x3 convolutions, its recogniser's
+tail and its bias-free 1x1 convolutions with the shortcuts' BatchNorms.
 
 The 22 depthwise convolutions of the network (`_SeparableBlock.conv_sep1[0]`, `_SeparableBlock.conv2[0]`, `_smooth(...)[0]`
 in upconv1 / upconv2; tools/models.py:70-102 of the reference) are the largest single item of the end-to-end chain's
@@ -43,6 +44,15 @@ do no arithmetic worth one: nine functional LeakyReLUs, and a bias add and a log
 -- `conv11`, its bias, the log-softmax -- is one launch, `rroi_align._ext.rroi_align.ocr_head`, each step
 where its own predicate holds (`fused_norm_ok`, `conv3x3_ok`, `act_pool_ok`, `ocr_head_ok`) and the stock expression
 otherwise.  `conv10_s` stays stock.
+
+The 29 bias-free 1x1 convolutions -- the pointwise halves of the separable blocks of `layer3` / `layer4`, the three
+shortcuts `layerN.0.downsample[0]`, the laterals `feature1` - `feature4` and the pointwise halves of `upconv1` / `upconv2`
+-- are the largest group of launches left on stock kernels.  In bfloat16 / float16 `use_native_conv1x1(net)` switches them
+to `PointwiseConv1x1`, which calls `rroi_align._ext.rroi_align.conv1x1` (a GEMM per image on the matrix
+cores, one launch) wherever `conv1x1_ok` holds and `nn.Conv2d.forward` otherwise, and the three shortcut pairs
+(convolution, `nn.BatchNorm2d`) to `NativeShortcut`, which folds the eval-mode norm into that one launch wherever
+`shortcut_ok` holds.  float32 inputs always take the stock path, and so does every shape class `_conv1x1_slower` lists.
+The five 1x1 convolutions with a bias belong to the heads and the recogniser's head above.
 """
 import torch
 import torch.nn as nn
@@ -712,3 +722,128 @@ def use_native_recogniser(net: nn.Module, enable: bool = True) -> bool:
     return _switch_class(net, ((FOTSNet, NativeRecogniserFOTSNet), (NativeHeadsFOTSNet, NativeHeadsRecogniserFOTSNet),
                                (NativeMergeFOTSNet, NativeMergeRecogniserFOTSNet),
                                (NativeHeadsMergeFOTSNet, NativeHeadsMergeRecogniserFOTSNet)), enable)
+
+
+# --------------------------------------------------------------------------- the 1x1 convolutions, DESIGN 5.17
+def _pointwise_static_ok(m) -> bool:
+    """What of `conv1x1_ok` depends on the module alone: an exact 1x1, no padding, stride 1 or 2, groups 1, no bias."""
+    return (m.kernel_size == (1, 1) and m.padding == (0, 0) and m.dilation == (1, 1) and m.stride in ((1, 1), (2, 2))
+            and m.groups == 1 and m._parameters["bias"] is None and m.padding_mode == "zeros")
+
+
+def conv1x1_ok(m, x) -> bool:
+    """True where `m(x)` may run the native matrix-core kernel: pure, no GPU needed to ask.  A 16-bit dtype equal to the
+    weight's (float32 keeps the stock path), a contiguous CUDA 4-D input of fewer than 2^31 elements whose output stays
+    below that too, a contiguous weight on x's device, no autocast, no gradient needed, and not one of the shape classes
+    that measured slower (`_conv1x1_slower`)."""
+    w = m._parameters["weight"]
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype == w.dtype and x.dtype in _CONV_DTYPES
+            and x.is_contiguous() and _pointwise_static_ok(m) and x.size(1) == m.in_channels and w.device == x.device
+            and w.is_contiguous() and 0 < x.numel() < (1 << 31)):
+        return False
+    s = m.stride[0]
+    return (x.size(0) * m.out_channels * ((x.size(2) - 1) // s + 1) * ((x.size(3) - 1) // s + 1) < (1 << 31)
+            and not _conv1x1_slower(m, x)
+            and not torch.is_autocast_enabled()
+            and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)))
+
+
+def _conv1x1_slower(m, x) -> bool:
+    """The shape classes in which the native kernel's median was not below the stock one's (profiles/native_conv1x1.md,
+    microseconds per call, native / stock, bf16 | fp16; a shortcut with its norm against `F.conv2d` + eval `BatchNorm2d`).
+    With M = N * Cout * Ho * Wo * Cin multiply-adds: M above 5.5e9, at either stride -- the large maps of eight images,
+    where the stock GEMM streams faster than this kernel's 2-byte stores: 64>256 at 176x320 x 8 (M 7.4e9) 86.7/74.2 |
+    86.5/71.4, 256>256 at 88x160 x 8 (7.4e9) 50.4/49.8 | 51.5/51.2, 256>256 at 176x320 x 8 (29.5e9) 206/124 | 209/125.
+    Below the line every measured row wins, 54 of 60: the nearest are 128>256 at 88x160 x 8 (3.7e9) 33.6/44.1 | 34.1/44.4
+    and 256>256 at 176x320 x 1 (3.7e9) 28.5/45.4 | 29.0/45.5; every shape of one image does, 9.2-16.9 against 44.8-60.2
+    (the stock path is a chain of launches there, bound by what the host can issue); the line is drawn between the nearest
+    measured rows on either side, 3.7e9 and 7.4e9."""
+    s = m.stride[0]
+    return x.size(0) * m.out_channels * ((x.size(2) - 1) // s + 1) * ((x.size(3) - 1) // s + 1) * m.in_channels > 5.5e9
+
+
+class PointwiseConv1x1(nn.Conv2d):
+    """An `nn.Conv2d` (same parameters, same `state_dict` keys) whose forward runs the native matrix-core kernel where
+    `conv1x1_ok(self, x)` holds."""
+
+    def forward(self, x):
+        if conv1x1_ok(self, x):
+            return _ext()._conv1x1_run(x, self._parameters["weight"], self.stride[0])
+        return super().forward(x)
+
+
+def _shortcut_pair(seq):
+    """(convolution, norm) of a Sequential whose modules are exactly a qualifying 1x1 convolution and an `nn.BatchNorm2d`;
+    None otherwise."""
+    mods = list(seq._modules.values())
+    if len(mods) != 2:
+        return None
+    conv, bn = mods
+    if type(conv) not in (nn.Conv2d, PointwiseConv1x1) or type(bn) is not nn.BatchNorm2d or not _pointwise_static_ok(conv):
+        return None
+    return conv, bn
+
+
+def shortcut_ok(seq, x) -> bool:
+    """True where `seq(x)` -- a 1x1 convolution and the `nn.BatchNorm2d` behind it -- may run as ONE native call with the
+    norm folded in: pure, no GPU needed to ask.  `conv1x1_ok` for the convolution, and a norm in eval mode that tracks
+    running statistics and has both buffers, of the convolution's `out_channels`, its buffers and its parameters (both or
+    neither) of x's dtype on x's device, none of which needs a gradient."""
+    pair = _shortcut_pair(seq)
+    if pair is None:
+        return False
+    conv, bn = pair
+    if not conv1x1_ok(conv, x):
+        return False
+    mean, var = bn._buffers.get("running_mean"), bn._buffers.get("running_var")
+    g, b = bn._parameters.get("weight"), bn._parameters.get("bias")
+    if bn.training or not bn.track_running_stats or mean is None or var is None or bn.num_features != conv.out_channels:
+        return False
+    if (g is None) != (b is None):
+        return False
+    vectors = (mean, var) if g is None else (mean, var, g, b)
+    return (all(v.dtype == x.dtype and v.device == x.device and v.is_contiguous() for v in vectors)
+            and not (torch.is_grad_enabled() and g is not None and (g.requires_grad or b.requires_grad)))
+
+
+class NativeShortcut(nn.Sequential):
+    """An `nn.Sequential` of (1x1 convolution, `nn.BatchNorm2d`) -- the shortcut of a stage's first block; same modules,
+    same `state_dict` keys -- that runs as one native call with the norm folded in where `shortcut_ok(self, x)` holds;
+    otherwise the Sequential's own forward, which still runs a switched convolution natively and the stock norm."""
+
+    def forward(self, x):
+        if shortcut_ok(self, x):
+            conv, bn = self._modules.values()
+            return _ext()._conv1x1_run(x, conv._parameters["weight"], conv.stride[0], 1.0,
+                                       (bn._parameters.get("weight"), bn._parameters.get("bias"),
+                                        bn._buffers["running_mean"], bn._buffers["running_var"], bn.eps))
+        return super().forward(x)
+
+
+def use_native_conv1x1(net: nn.Module, enable: bool = True):
+    """Switch every qualifying `nn.Conv2d` of `net` -- by exact type: a 1x1, no padding, stride 1 or 2, groups 1, no bias
+    -- to `PointwiseConv1x1` (29 for `FOTSNet()`), and every `nn.Sequential` -- by exact type -- whose modules are exactly
+    such a convolution and an `nn.BatchNorm2d` to `NativeShortcut` (3 for `FOTSNet()`).  enable=False: every class back.
+    Only classes change: no parameter is copied, no key of the state_dict moves; the other switches test exact types, so
+    they leave these classes alone and compose with this one in any order.  Whether a call runs the native kernel is
+    decided per call by `conv1x1_ok` / `shortcut_ok` (float32 never does).  Returns (convolutions switched, shortcuts
+    switched)."""
+    convs = shortcuts = 0
+    if not enable:
+        for m in net.modules():
+            if type(m) is PointwiseConv1x1:
+                m.__class__ = nn.Conv2d
+                convs += 1
+            elif type(m) is NativeShortcut:
+                m.__class__ = nn.Sequential
+                shortcuts += 1
+        return convs, shortcuts
+    for m in net.modules():
+        if type(m) is nn.Conv2d and _pointwise_static_ok(m):
+            m.__class__ = PointwiseConv1x1
+            convs += 1
+    for m in net.modules():
+        if type(m) is nn.Sequential and _shortcut_pair(m) is not None:
+            m.__class__ = NativeShortcut
+            shortcuts += 1
+    return convs, shortcuts

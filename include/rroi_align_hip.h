@@ -779,6 +779,59 @@ int rroi_ocr_head_plan(int dtype, int batch_size, int channels, int classes, int
 int rroi_act_maxpool2x1_forward_hip(int dtype, const void* x, void* y, int batch_size, int channels, int height, int width,
                                     float negative_slope, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * 11. The network's bias-free 1x1 convolutions on the matrix cores, bfloat16 / float16, with the BatchNorm of a shortcut
+ *    folded in, in ONE launch.  Forward only; opt-in from Python (fots_e2e.native.use_native_conv1x1).
+ *
+ *      y[n,k,i,j] = act( s[k] * sum_c w[k,c] * x[n,c,S*i,S*j] + t[k] )
+ *
+ *      x   (N, Cin, H, W)      w   (Cout, Cin) -- the contiguous (Cout, Cin, 1, 1) weight      y   (N, Cout, Ho, Wo),
+ *      Ho = (H - 1) / S + 1, Wo likewise, S = stride, 1 or 2
+ *    all contiguous NCHW of one 16-bit element type `dtype` (RROI_DTYPE_BF16 / RROI_DTYPE_FP16); no bias, groups 1; any
+ *    Cin >= 1 and Cout >= 1.  act(v) = v < 0 ? v * negative_slope : v in fp32: 1.0 is no activation, 0.0 a ReLU.
+ *
+ *    The norm: bn_mean and bn_var (Cout each, both or neither), bn_weight and bn_bias (Cout each, both or both NULL: 1
+ *    and 0), of the tensors' type, and eps.  s = g / sqrt(var + eps), t = b - mean * s, computed in fp32 by every workgroup
+ *    for its own channel rows: no cache of folded parameters, no workspace.  With all four NULL no norm is applied: s and t
+ *    do not exist and the result is the bare fp32 sum, rounded once.  bn_weight and bn_bias without bn_mean and bn_var
+ *    are refused.
+ *
+ *    Every element of y is written and nothing else is; nothing outside x, w and the vectors is read; y may overlap no
+ *    input.  Any element-aligned x, w, y and vectors work (16-byte loads are decided per item inside the kernel).
+ *
+ *    Arithmetic: a GEMM per image on v_mfma_f32_32x32x16_{bf16,f16} with fp32 accumulators; products of two 16-bit values
+ *    are exact in fp32; Cin is summed in an order the plan fixes (no atomic, no split of K across workgroups), so repeated
+ *    calls give the same bits; s * sum + t as one fp32 multiply and one fp32 add; ONE rounding from fp32 to the tensor's
+ *    type, after the activation.  With ref the exact sum, A that of |w| |x|, u = 2^-8 (bf16) / 2^-11 (fp16):
+ *      no norm:  |y - act(ref)| <= Cin 2^-23 A + u |act(ref)| (+ 2^-25 in fp16's subnormal range)
+ *      norm:     |y - act(z)| <= |s| Cin 2^-23 A + 2^-20 (|s| (A + |mean|) + |b|) + u |act(z)| (+ 2^-25),  z = s ref + t
+ *
+ *    Returns 1 / 0 / -hipError.  0, before any launch: fp32 or an unknown dtype, a dimension below 1, a stride other than
+ *    1 or 2, x, w or y of 2^31 elements or more, a NULL x, w or y, a non-finite negative_slope, a non-finite or negative
+ *    eps, bn_weight and bn_bias not both NULL or both given, bn_mean and bn_var likewise, an affine pair without
+ *    statistics.  Each call enqueues one kernel on `stream`, allocates nothing and can be captured into a HIP graph.
+ *    Arrived after 0.10.0 under the same version string: detect it by symbol.
+ * ------------------------------------------------------------------------- */
+typedef struct rroi_conv1x1_plan_info {
+    int tile_m;      /* output channels per workgroup: 32 or 64 */
+    int tile_p;      /* output pixels per workgroup, flat over the output plane: 128 (32 per wave) */
+    int k_chunk;     /* input channels staged through LDS at a time: 64 */
+    int k_chunks;    /* ceil(Cin / k_chunk) */
+    int m_tiles, p_tiles;   /* tiles per image along Cout and along Ho * Wo */
+    int grid_x;      /* workgroups: N * m_tiles * p_tiles */
+    int block;       /* threads per workgroup: 256 */
+    int lds_bytes;   /* the chunk's pixels and weights + the folded norm of the tile's channels */
+    int out_h, out_w;
+    int reserved;
+} rroi_conv1x1_plan_info;
+int rroi_conv1x1_forward_hip(int dtype, const void* x, const void* w, void* y, int batch_size, int in_channels,
+                             int out_channels, int height, int width, int stride, float negative_slope,
+                             const void* bn_weight, const void* bn_bias, const void* bn_mean, const void* bn_var, double eps,
+                             void* stream);
+/* host only, no launch; 1, or 0 for arguments the call would refuse */
+int rroi_conv1x1_plan(int dtype, int batch_size, int in_channels, int out_channels, int height, int width, int stride,
+                      rroi_conv1x1_plan_info* plan);
+
 /* Bin centres only: geom (R, PH, PW, 2) = (bin_cx, bin_cy), 0 where the bin is
  * outside the ROI's pooled width (kernel.cu:86-107).  Diagnostic / test hook. */
 int rroi_align_bin_centres_hip(float spatial_scale, int num_rois, int height, int width,
@@ -810,7 +863,8 @@ int rroi_align_get_trig_recipe_hip(void);
  * The typed callers' entry points (rroi_rbox_decode_typed_hip, rroi_ctc_greedy_decode_typed_hip) arrived after 0.10.0 under
  * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b, the depthwise
  * convolution of section 5, the InstanceNorm of section 6, its fused epilogues of section 6b, the heads and gate of section 7, the gated merge
- * of section 8, the dense 3x3 convolution of section 9 and the recogniser's head and activation + pool of section 10. */
+ * of section 8, the dense 3x3 convolution of section 9, the recogniser's head and activation + pool of section 10 and the 1x1
+ * convolution of section 11. */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
