@@ -32,7 +32,10 @@
 // DESIGN 5.14), rroi_conv3x3_kernels.h (+ rroi_conv3x3_host.h: its dense 3x3 convolutions on the matrix cores, bfloat16 /
 // float16), rroi_recogniser_kernels.h (+ rroi_recogniser_host.h: the recogniser's log-softmax head and its
 // activation + (2,1) max-pool), rroi_conv1x1_kernels.h (+ rroi_conv1x1_host.h: its bias-free 1x1 convolutions on
-// the matrix cores with the shortcut's BatchNorm folded in, bfloat16 / float16).  Host side: rroi_host_plan.h (tuning table,
+// the matrix cores with the shortcut's BatchNorm folded in, bfloat16 / float16), rroi_conv2x3_kernels.h
+// (+ rroi_conv2x3_host.h: the recogniser's (2,3) convolution on the matrix cores, bfloat16 / float16),
+// rroi_updw_kernels.h (+ rroi_updw_host.h: the bilinear resize and the depthwise 3x3 behind it in one launch).
+// Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
 // launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
 #include <hip/hip_runtime.h>
@@ -68,6 +71,8 @@ namespace {
 #include "rroi_conv3x3_kernels.h"
 #include "rroi_recogniser_kernels.h"
 #include "rroi_conv1x1_kernels.h"
+#include "rroi_conv2x3_kernels.h"
+#include "rroi_updw_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
@@ -79,6 +84,8 @@ namespace {
 #include "rroi_conv3x3_host.h"
 #include "rroi_recogniser_host.h"
 #include "rroi_conv1x1_host.h"
+#include "rroi_conv2x3_host.h"
+#include "rroi_updw_host.h"
 
 }  // namespace
 
@@ -903,6 +910,53 @@ int rroi_conv1x1_forward_forced_hip(int dtype, const void* x, const void* w, voi
                         bn_bias, bn_mean, bn_var, eps, stream);
 }
 #endif
+
+// ------------------------------------------------------------------------------------
+// The recogniser's (2,3) convolution on the matrix cores, bfloat16 / float16 (header section 12): one launch,
+// no workspace.
+// ------------------------------------------------------------------------------------
+int rroi_conv2x3_plan(int dtype, int batch_size, int in_channels, int out_channels, int height, int width,
+                      rroi_conv2x3_plan_info* plan)
+{
+    const Conv2x3Plan P = plan_conv2x3(dtype, batch_size, in_channels, out_channels, height, width);
+    if (!P.status || !plan) return 0;
+    *plan = rroi_conv2x3_plan_info{32, kC2TileW, kC2Items, kC2KC, (int)P.k_chunks, (int)P.m_tiles, (int)P.x_tiles,
+                                   (int)P.items, (int)P.grid, kC2Threads, kC2LdsBytes, P.Ho, width, 0};
+    return 1;
+}
+
+int rroi_conv2x3_forward_hip(int dtype, const void* x, const void* w, void* y, int batch_size, int in_channels,
+                             int out_channels, int height, int width, float negative_slope, void* stream_)
+{
+    const Conv2x3Plan P = plan_conv2x3(dtype, batch_size, in_channels, out_channels, height, width);
+    if (!P.status) return 0;
+    if (!x || !w || !y) return 0;
+    if (!std::isfinite(negative_slope)) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (dtype == RROI_DTYPE_BF16)
+        return launch_conv2x3(P, static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(w), static_cast<bf16_t*>(y),
+                              (unsigned)in_channels, (unsigned)out_channels, (unsigned)height, (unsigned)width,
+                              negative_slope, stream);
+    return launch_conv2x3(P, static_cast<const fp16_t*>(x), static_cast<const fp16_t*>(w), static_cast<fp16_t*>(y),
+                          (unsigned)in_channels, (unsigned)out_channels, (unsigned)height, (unsigned)width, negative_slope,
+                          stream);
+}
+
+// ------------------------------------------------------------------------------------
+// Bilinear resize + depthwise 3x3 convolution (header section 13): one launch, no workspace.
+// ------------------------------------------------------------------------------------
+int rroi_up_depthwise3x3_forward_hip(int dtype, const void* a, const void* weight, void* y, int batch_size, int channels,
+                                     int in_height, int in_width, int out_height, int out_width, void* stream_)
+{
+    if (!updw_shape_ok(dtype, batch_size, channels, in_height, in_width, out_height, out_width)) return 0;
+    if (!a || !weight || !y) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_updw(static_cast<const T*>(a), static_cast<const T*>(weight), static_cast<T*>(y), batch_size, channels,
+                           in_height, in_width, out_height, out_width, stream);
+    });
+}
 
 int rroi_align_set_trig_recipe_hip(int recipe) { return recipe == RROI_TRIG_DOUBLE ? 1 : 0; }   // deprecated shim, see the header
 int rroi_align_get_trig_recipe_hip(void) { return RROI_TRIG_DOUBLE; }

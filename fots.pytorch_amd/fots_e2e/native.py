@@ -24,7 +24,8 @@ holds, the stock methods otherwise.  The same terms once more.
 The feature merge between them -- three times `up(a) + f * up(gate)`: a bilinear resize of the one-channel gate, a multiply
 and an add over a 256-channel map, in the first merge also a resize of the coarser map -- is one launch per merge after
 `use_native_merge(net)`: `rroi_align._ext.rroi_align.gated_merge` wherever `merge_ok` holds, the stock
-expression otherwise.  The resize in front of `upconv1` / `upconv2` and the `upconv` blocks stay stock.
+expression otherwise.  The resize in front of `upconv1` / `upconv2` stays stock here: `fots_e2e.native_remainder` folds it into
+the depthwise half of the block (`use_native_upconv`), and `_merge` hands such a block the map before its resize.
 
 What `model.py` applies functionally around its norms -- the stem's `cat(x, -x)` and LeakyReLU in `_MirrorNorm` (twice per
 pass, on the two largest tensors of the network), the ReLU behind `_PlainBlock.bn1`, and the shortcut add and activation
@@ -43,7 +44,7 @@ do no arithmetic worth one: nine functional LeakyReLUs, and a bias add and a log
 `_instance_norm_run`) or behind it (`rroi_align._ext.rroi_align.act_maxpool2x1`: LeakyReLU + (2,1) max-pool), and the tail
 -- `conv11`, its bias, the log-softmax -- is one launch, `rroi_align._ext.rroi_align.ocr_head`, each step
 where its own predicate holds (`fused_norm_ok`, `conv3x3_ok`, `act_pool_ok`, `ocr_head_ok`) and the stock expression
-otherwise.  `conv10_s` stays stock.
+otherwise.  `conv10_s` stays stock here (`fots_e2e.native_remainder.use_native_conv2x3` switches it).
 
 The 29 bias-free 1x1 convolutions -- the pointwise halves of the separable blocks of `layer3` / `layer4`, the three
 shortcuts `layerN.0.downsample[0]`, the laterals `feature1` - `feature4` and the pointwise halves of `upconv1` / `upconv2`
@@ -314,7 +315,8 @@ def _merge_slower(a, f, gate) -> bool:
 class _NativeMerge:
     """Mixin in front of a `FOTSNet`: `_merge` runs each of the three merges, `up(a) + f * up(gate)`, as one native call
     where `merge_ok` holds, and as the stock expression where it does not.  The resize in front of `upconv1` / `upconv2`
-    stays stock.  A network in training mode takes the stock method."""
+    stays stock unless the block takes the unresized map itself (`_smoothed`).  A network in training mode takes the stock
+    method."""
 
     def _low_gate(self, t):
         """The gate at its source's size, before the resize: the native gate where the network has it."""
@@ -330,12 +332,17 @@ class _NativeMerge:
         A = a if a.shape[2:] == f.shape[2:] else self._up(a, f)
         return A + f if g is None else A + f * self._up(g, f)
 
+    def _smoothed(self, upconv, t, like):
+        """upconv(up(t, like)); a block that can take the map before its resize (`native_remainder.UpSmooth`) is given it."""
+        resized = getattr(upconv, "forward_resized", None)
+        return upconv(self._up(t, like)) if resized is None else resized(t, like)
+
     def _merge(self, f1, f2, f3, f4):
         if self.training:
             return super()._merge(f1, f2, f3, f4)
         t = self._merge_one(f4, f3, f4)
-        m2 = self._merge_one(self.upconv1(self._up(t, f2)), f2, t)
-        m1 = self._merge_one(self.upconv2(self._up(m2, f1)), f1, m2)
+        m2 = self._merge_one(self._smoothed(self.upconv1, t, f2), f2, t)
+        m1 = self._merge_one(self._smoothed(self.upconv2, m2, f1), f1, m2)
         return m1, m2
 
 

@@ -832,6 +832,71 @@ int rroi_conv1x1_forward_hip(int dtype, const void* x, const void* w, void* y, i
 int rroi_conv1x1_plan(int dtype, int batch_size, int in_channels, int out_channels, int height, int width, int stride,
                       rroi_conv1x1_plan_info* plan);
 
+/* ------------------------------------------------------------------------- *
+ * 12. The recogniser's (2,3) convolution on the matrix cores, bfloat16 / float16:
+ *    y = act(conv2d(x, w, stride 1, padding (0, 1))) in ONE launch.  Forward only; opt-in from Python
+ *    (fots_e2e.native_remainder.use_native_conv2x3).  Section 9's conventions.
+ *
+ *      x   (N, Cin, H, W), H >= 2      w   (Cout, Cin, 2, 3)      y   (N, Cout, H - 1, W)
+ *    all contiguous NCHW of one 16-bit element type `dtype` (RROI_DTYPE_BF16 / RROI_DTYPE_FP16); no bias, groups 1,
+ *    dilation 1; any Cin >= 1, Cout >= 1 and W >= 1.  act(v) = v < 0 ? v * negative_slope : v in fp32: 1.0 is no
+ *    activation, 0.0 a ReLU.  Every element of y is written once and nothing else is; nothing outside x and w is read (the
+ *    padding is a zero fill inside the kernel); y may overlap no input.  Any element-aligned x, w and y work.
+ *
+ *    Arithmetic: an implicit GEMM on v_mfma_f32_32x32x16_{bf16,f16} with fp32 accumulators; K = (ky, kx, cin) is summed in
+ *    a fixed order (no atomic, no split of K), so repeated calls give the same bits; ONE rounding from fp32 to the tensor's
+ *    type, after the activation.  With ref the exact convolution and S that of |x| with |w|,
+ *    |y - act(ref)| <= 6 Cin 2^-23 S + u |act(ref)| (+ 2^-25 in fp16), u = 2^-8 (bf16) / 2^-11 (fp16).
+ *
+ *    Returns 1 / 0 / -hipError.  0, before any launch: fp32 or an unknown dtype, H < 2, another dimension below 1, x, w or
+ *    y of 2^31 elements or more, a NULL x, w or y, a non-finite negative_slope.  Each call enqueues one kernel on
+ *    `stream`, uses no workspace, allocates nothing and can be captured into a HIP graph.  Arrived after 0.10.0 under the
+ *    same version string: detect it by symbol.
+ * ------------------------------------------------------------------------- */
+typedef struct rroi_conv2x3_plan_info {
+    int tile_m;      /* output channels per workgroup: 32 */
+    int tile_w;      /* output columns per item: 32 */
+    int wave_items;  /* items (one output row x tile_w columns of one image) per workgroup, one per wave: 4 */
+    int k_chunk;     /* input channels staged through LDS at a time: 32 */
+    int k_chunks;    /* ceil(Cin / k_chunk) */
+    int m_tiles;     /* ceil(Cout / tile_m) */
+    int x_tiles;     /* ceil(W / tile_w) */
+    int items;       /* N * (H - 1) * x_tiles */
+    int grid_x;      /* workgroups: ceil(items / wave_items) * m_tiles */
+    int block;       /* threads per workgroup: 256 */
+    int lds_bytes;   /* the items' input tiles with their halo columns + the chunk's weights, rows padded by 8 elements */
+    int out_h, out_w;
+    int reserved;
+} rroi_conv2x3_plan_info;
+int rroi_conv2x3_forward_hip(int dtype, const void* x, const void* w, void* y, int batch_size, int in_channels,
+                             int out_channels, int height, int width, float negative_slope, void* stream);
+/* host only, no launch; 1, or 0 for arguments the call would refuse */
+int rroi_conv2x3_plan(int dtype, int batch_size, int in_channels, int out_channels, int height, int width,
+                      rroi_conv2x3_plan_info* plan);
+
+/* ------------------------------------------------------------------------- *
+ * 13. Bilinear resize + depthwise 3x3 convolution in ONE launch: y = depthwise3x3(U, w), stride 1,
+ *    padding 1, where U is `a` resized to (out_height, out_width) and rounded to the tensors' type -- the resize in front
+ *    of the network's `upconv1` / `upconv2` with the depthwise half of the block.  Forward only; opt-in from Python
+ *    (fots_e2e.native_remainder.use_native_upconv).
+ *
+ *      a   (N, C, in_height, in_width)      w   (C, 1, 3, 3)      y   (N, C, out_height, out_width)
+ *    all contiguous NCHW of one element type `dtype` (fp32, bf16 or fp16); any sizes >= 1 on both sides.
+ *
+ *    Arithmetic: U[n, c] = (T)(float) of section 8's resize (bilinear, align_corners = true, in double, the scale
+ *    (in - 1) / (out - 1) computed on the host, 0 where out == 1, every operation rounded to double; a source that already
+ *    has the target's size is read as it is), then section 5's recipe on those rounded values: a double accumulator, ky
+ *    then kx ascending, a tap outside U is w * (+0.0) and is never skipped, the result (T)(float)acc.  So y is, bit for
+ *    bit, what rroi_depthwise3x3_forward_hip gives on the rounded resized map; that map is never stored.
+ *
+ *    Returns 1 / 0 / -hipError.  0, before any launch: an unknown dtype, a dimension below 1, a or y of 2^31 elements or
+ *    more, a NULL a, w or y.  Each call enqueues one kernel on `stream`, uses no workspace, allocates nothing, works for any
+ *    element-aligned addresses and can be captured into a HIP graph.  Arrived after 0.10.0 under the same version string:
+ *    detect it by symbol.
+ * ------------------------------------------------------------------------- */
+int rroi_up_depthwise3x3_forward_hip(int dtype, const void* a, const void* weight, void* y, int batch_size, int channels,
+                                     int in_height, int in_width, int out_height, int out_width, void* stream);
+
 /* Bin centres only: geom (R, PH, PW, 2) = (bin_cx, bin_cy), 0 where the bin is
  * outside the ROI's pooled width (kernel.cu:86-107).  Diagnostic / test hook. */
 int rroi_align_bin_centres_hip(float spatial_scale, int num_rois, int height, int width,
