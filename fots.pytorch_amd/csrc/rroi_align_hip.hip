@@ -34,7 +34,8 @@
 // activation + (2,1) max-pool), rroi_conv1x1_kernels.h (+ rroi_conv1x1_host.h: its bias-free 1x1 convolutions on
 // the matrix cores with the shortcut's BatchNorm folded in, bfloat16 / float16), rroi_conv2x3_kernels.h
 // (+ rroi_conv2x3_host.h: the recogniser's (2,3) convolution on the matrix cores, bfloat16 / float16),
-// rroi_updw_kernels.h (+ rroi_updw_host.h: the bilinear resize and the depthwise 3x3 behind it in one launch).
+// rroi_updw_kernels.h (+ rroi_updw_host.h: the bilinear resize and the depthwise 3x3 behind it in one launch),
+// rroi_preprocess_kernels.h (+ rroi_preprocess_host.h: uint8 images to the network's input tensor in one launch).
 // Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
 // launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
@@ -73,6 +74,7 @@ namespace {
 #include "rroi_conv1x1_kernels.h"
 #include "rroi_conv2x3_kernels.h"
 #include "rroi_updw_kernels.h"
+#include "rroi_preprocess_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
@@ -86,6 +88,7 @@ namespace {
 #include "rroi_conv1x1_host.h"
 #include "rroi_conv2x3_host.h"
 #include "rroi_updw_host.h"
+#include "rroi_preprocess_host.h"
 
 }  // namespace
 
@@ -955,6 +958,31 @@ int rroi_up_depthwise3x3_forward_hip(int dtype, const void* a, const void* weigh
         typedef decltype(tag) T;
         return launch_updw(static_cast<const T*>(a), static_cast<const T*>(weight), static_cast<T*>(y), batch_size, channels,
                            in_height, in_width, out_height, out_width, stream);
+    });
+}
+
+// ------------------------------------------------------------------------------------
+// Native preprocessing (header section 14): uint8 images to the network's input, one launch, no workspace.
+// ------------------------------------------------------------------------------------
+int rroi_preprocess_plan(int dtype, int batch_size, int out_height, int out_width, rroi_preprocess_plan_info* plan)
+{
+    const PreprocessPlan P = plan_preprocess(dtype, batch_size, out_height, out_width);
+    if (!P.status || !plan) return 0;
+    *plan = rroi_preprocess_plan_info{(int)P.grid, kPpThreads, P.V, P.band, (int)P.nstrips, (int)P.nbands, (int)P.items, P.wide};
+    return 1;
+}
+
+int rroi_preprocess_forward_hip(int dtype, const unsigned char* src, const int* table, void* y, int batch_size,
+                                int out_height, int out_width, void* stream_)
+{
+    const PreprocessPlan P = plan_preprocess(dtype, batch_size, out_height, out_width);
+    if (!P.status) return 0;
+    if (batch_size == 0) return 1;
+    if (!src || !table || !y) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_preprocess(P, src, table, static_cast<T*>(y), out_height, out_width, stream);
     });
 }
 

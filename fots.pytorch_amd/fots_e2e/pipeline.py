@@ -17,6 +17,9 @@ launch, the head, `max(1)`, a Python decode) is not part of this package: it liv
 (`oracle/e2e_loop_oracle.py`), where the tests compare the two and `bench_e2e.py` times it as the baseline.
 """
 
+import collections
+import threading
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -54,6 +57,130 @@ def preprocess(im_u8, device, dtype=torch.float32):
         t = F.interpolate(t, size=(h, w), mode="bilinear", align_corners=False)
     t = t / 128 - 1
     return t if dtype == torch.float32 else t.to(dtype)
+
+
+def _one_size(ims):
+    """The one (H, W) that `resize_rule` maps every image of a batch to; ValueError where they differ."""
+    sizes = {resize_rule(im.shape[0], im.shape[1]) for im in ims}
+    if len(sizes) != 1:
+        raise ValueError("infer_batch: the images must resize to one size, got %s (group them by size)" % sorted(sizes))
+    return sizes.pop()
+
+
+def preprocess_ok(ims, device, dtype=torch.float32) -> bool:
+    """Whether `preprocess_batch` can stand in for `preprocess` on these images (a pure predicate: no GPU, no library):
+    a non-empty list of C-contiguous uint8 (H, W, 3) arrays that `resize_rule` maps to ONE size of at least one pixel, a
+    CUDA device, one of the three dtypes, fewer than 2^31 bytes to upload and fewer than 2^31 elements to write, and not
+    one of the classes that measured slower (`_preprocess_slower`)."""
+    if not isinstance(ims, (list, tuple)) or len(ims) == 0:
+        return False
+    try:
+        if torch.device(device).type != "cuda":
+            return False
+    except (TypeError, RuntimeError):
+        return False
+    if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        return False
+    for im in ims:
+        if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3
+                and im.flags["C_CONTIGUOUS"] and im.shape[0] >= 1 and im.shape[1] >= 1):
+            return False
+    sizes = {resize_rule(im.shape[0], im.shape[1]) for im in ims}
+    if len(sizes) != 1:
+        return False
+    h, w = next(iter(sizes))
+    if h < 1 or w < 1:
+        return False
+    if sum(im.size for im in ims) >= (1 << 31) or len(ims) * 3 * h * w >= (1 << 31):
+        return False
+    return not _preprocess_slower(len(ims), (h, w), dtype)
+
+
+def _preprocess_slower(n_images, size, dtype) -> bool:
+    """The classes in which the native call's median was not below the stock chain's (profiles/native_preprocess.md,
+    tools/preprocess_bench.py; per call, 720 x 1280 > 704 x 1280, microseconds, native / stock, fp32 | bf16 | fp16): none.
+    All 12 rows win.  Between device events, the bytes already uploaded: one image 9.3 / 33.2 | 9.4 / 37.6 | 9.6 / 37.4,
+    eight 24.3 / 300.5 | 28.5 / 330.8 | 28.5 / 329.1.  By the host clock, upload included, as the pipeline calls it: one
+    image 94.8 / 112.5 | 99.1 / 118.3 | 98.8 / 125.7 (the closest rows: the minimum of the stock arm, 112.3, is below the
+    maximum of the native one, 114.6), eight 568.4 / 912.3 | 561.8 / 957.0 | 608.5 / 983.3."""
+    return False
+
+
+_PP_TABLES = collections.OrderedDict()      # (device index, the images' sizes) -> (device table, byte offsets, total bytes)
+_PP_TABLES_MAX = 32
+_pp_tables_lock = threading.Lock()
+
+
+def _preprocess_table(ims, device):
+    """The kernel's table {byte offset, H0, W0, 0} for images of these sizes laid back to back, on `device`: built and
+    uploaded on first use and kept (a stream of images has a handful of sizes -- ICDAR 2015 has one -- so the table of a
+    batch is the table of the batch before it).  A kept table is written once, by a synchronous upload, before it is
+    returned, so a launch on any stream may read it; `preprocess_batch` records the stream that does (record_stream), so
+    that a table that ages out -- at most _PP_TABLES_MAX are kept, least recently used first out -- is not handed out again
+    under a launch that still reads it."""
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    key = (index,) + tuple(im.shape[:2] for im in ims)
+    with _pp_tables_lock:
+        ent = _PP_TABLES.get(key)
+        if ent is not None:
+            _PP_TABLES.move_to_end(key)
+            return ent
+    table = np.zeros((len(ims), 4), np.int32)
+    at = 0
+    for k, im in enumerate(ims):
+        table[k] = (at, im.shape[0], im.shape[1], 0)
+        at += im.size
+    ent = (torch.from_numpy(table).to(device), table[:, 0].tolist(), at)
+    with _pp_tables_lock:
+        _PP_TABLES[key] = ent
+        while len(_PP_TABLES) > _PP_TABLES_MAX:
+            _PP_TABLES.popitem(last=False)
+    return ent
+
+
+def preprocess_batch(ims, device, dtype=torch.float32):
+    """N images, each (H0, W0, 3) uint8, -> (N, 3, H, W) in `dtype`: what `torch.cat([preprocess(im, device, dtype) ...])`
+    computes, by ONE launch (rroi_align._ext.rroi_align.preprocess).  Every image's bytes go up as they are,
+    straight from its array into its place in one device buffer -- the images back to back, at whatever address that is --
+    and the kernel reads them there, resizes (half-pixel bilinear, like `preprocess`), scales and rounds ONCE from double;
+    the table that tells it where each image lies is kept on the device per set of sizes (`_preprocess_table`).  Per call:
+    N uploads and one launch, against N uploads and 5 to 6 launches per image plus a `torch.cat`.  (Packing the images and
+    the table into one host buffer first, for ONE upload, was measured and is not done: copying eight 720 x 1280 images
+    on the host takes the 0.38 ms that the single upload saves twice over -- profiles/native_preprocess.md.)
+    Where no resize is needed the float32 result is `preprocess`'s bit for bit; where one is, it is the closer of the two
+    to the exact value (`preprocess` resizes in fp32).  The source sizes may differ as long as `resize_rule` maps them to
+    one size (the ValueError of `infer_batch` otherwise).  The buffer and the result are allocated, written and read on the
+    current stream."""
+    from rroi_align._ext.rroi_align import preprocess as _pp
+    if len(ims) == 0:
+        raise ValueError("preprocess_batch: no images")
+    ims = [np.ascontiguousarray(im) for im in ims]
+    for im in ims:
+        if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+            raise TypeError("preprocess_batch: every image must be an (H, W, 3) uint8 array, got %s %s" % (im.dtype, im.shape))
+    size = _one_size(ims)
+    if sum(im.size for im in ims) >= (1 << 31):
+        raise ValueError("preprocess_batch: the batch must be smaller than 2^31 bytes")
+    device = torch.device(device)
+    table, offsets, total = _preprocess_table(ims, device)
+    if len(ims) == 1:
+        src = torch.from_numpy(ims[0].reshape(-1)).to(device)
+    else:
+        src = torch.empty(total, dtype=torch.uint8, device=device)
+        for at, im in zip(offsets, ims):
+            src[at:at + im.size].copy_(torch.from_numpy(im.reshape(-1)))
+    out = _pp.preprocess_images(src, table, size, dtype)
+    table.record_stream(torch.cuda.current_stream(device))
+    return out
+
+
+def _front_input(ims, device, dtype, native_preprocess):
+    """The network's input for a list of images: `preprocess_batch` where it was asked for and `preprocess_ok` holds, the
+    stock expression otherwise."""
+    if native_preprocess and preprocess_ok(ims, device, dtype):
+        return preprocess_batch(ims, device, dtype)
+    _one_size(ims)
+    return torch.cat([preprocess(im, device, dtype) for im in ims], 0)
 
 
 def _net_device_dtype(net):
@@ -135,7 +262,8 @@ def batched(net, converter, features, boxes, return_crops=False, gw_host=None, b
     return (texts, crops, labels) if return_crops else texts
 
 
-def infer_image(net, converter, im, detector=None, segm_thresh=0.5, return_debug=False, bucketed=False):
+def infer_image(net, converter, im, detector=None, segm_thresh=0.5, return_debug=False, bucketed=False,
+                native_preprocess=False):
     """One image through the whole chain of `test.py:75-116`: preprocess -> net -> `get_boxes` on the maps
     where the network wrote them -> RoIRotate + recognition head + greedy CTC for every box ->
     (boxes (n, 9) numpy, texts); like the reference's loop, boxes whose text is empty are dropped
@@ -153,10 +281,17 @@ def infer_image(net, converter, im, detector=None, segm_thresh=0.5, return_debug
     The image is preprocessed into the dtype of the network's parameters (float32, bfloat16, float16), so
     `infer_image(net.to(torch.bfloat16), ...)` runs the whole chain in 16 bits with the same synchronisations; a tensor
     passed instead of an image is used as it is.  The `detector` hook's maps may have any of the three dtypes.
-    `bucketed`: see `batched` (opt-in; same boxes, texts and crops)."""
+    `bucketed`: see `batched` (opt-in; same boxes, texts and crops).
+    `native_preprocess` (opt-in): the image goes through `preprocess_batch` -- one upload, one launch -- where
+    `preprocess_ok` holds, through `preprocess` otherwise; the same input bit for bit in float32 where no resize is needed."""
     from rroi_align.nms import get_boxes
     device, dtype = _net_device_dtype(net)
-    im_data = preprocess(im, device, dtype) if not isinstance(im, torch.Tensor) else im
+    if isinstance(im, torch.Tensor):
+        im_data = im
+    elif native_preprocess and preprocess_ok([im], device, dtype):
+        im_data = preprocess_batch([im], device, dtype)
+    else:
+        im_data = preprocess(im, device, dtype)
     score, rbox, angle, feats = net(im_data)
     if detector is not None:
         s, r, a = detector(im_data)
@@ -171,7 +306,7 @@ def infer_image(net, converter, im, detector=None, segm_thresh=0.5, return_debug
     return res + ((boxes, out, feats),) if return_debug else res
 
 
-def _batch_front(net, ims, detector, segm_thresh):
+def _batch_front(net, ims, detector, segm_thresh, native_preprocess=False):
     """The first half of `infer_batch`, ENQUEUED on the current stream and nothing read back: preprocessing, one pass of the
     network, one decode launch per image."""
     from rroi_align.nms import decode_batch
@@ -179,10 +314,7 @@ def _batch_front(net, ims, detector, segm_thresh):
     if isinstance(ims, torch.Tensor):
         im_data = ims
     else:
-        sizes = {resize_rule(im.shape[0], im.shape[1]) for im in ims}
-        if len(sizes) != 1:
-            raise ValueError("infer_batch: the images must resize to one size, got %s (group them by size)" % sorted(sizes))
-        im_data = torch.cat([preprocess(im, device, dtype) for im in ims], 0)
+        im_data = _front_input(ims, device, dtype, native_preprocess)
     score, rbox, angle, feats = net(im_data)
     if detector is not None:
         s, r, a = detector(im_data)
@@ -212,7 +344,8 @@ def _batch_back(net, converter, front, return_debug=False, bucketed=False):
     return (res, (per_image, out, feats)) if return_debug else res
 
 
-def infer_batch(net, converter, ims, detector=None, segm_thresh=0.5, return_debug=False, bucketed=False):
+def infer_batch(net, converter, ims, detector=None, segm_thresh=0.5, return_debug=False, bucketed=False,
+                native_preprocess=False):
     """SEVERAL images of one size through the chain of `test.py:75-116` at once (round 6; the reference's loop takes one
     image per pass, `test.py:62-75` -- its test set, ICDAR 2015, is 1280 x 720 throughout): ONE pass through the network
     for the batch, `get_boxes` per image (every image's device decode is enqueued before the first read-back: one wait
@@ -223,20 +356,23 @@ def infer_batch(net, converter, ims, detector=None, segm_thresh=0.5, return_debu
 
     `ims`: a list of (H0, W0, 3) uint8 arrays that `resize_rule` maps to ONE size, or an (N, 3, H, W) tensor that is
     already preprocessed.  `detector`: as in `infer_image`, for the whole batch: `im_data -> (score (N, h, w),
-    rbox (N, 4, h, w), angle (N, 2, h, w))`."""
+    rbox (N, 4, h, w), angle (N, 2, h, w))`.  `native_preprocess` (opt-in): the whole batch goes through ONE
+    `preprocess_batch` -- one upload, one launch, no `torch.cat` -- where `preprocess_ok` holds (see `infer_image`)."""
     if len(ims) == 0:
         return ([], ([], ([], [], []), None)) if return_debug else []
-    return _batch_back(net, converter, _batch_front(net, ims, detector, segm_thresh), return_debug, bucketed)
+    return _batch_back(net, converter, _batch_front(net, ims, detector, segm_thresh, native_preprocess), return_debug, bucketed)
 
 
-def infer_stream(net, converter, batches, detector=None, segm_thresh=0.5, bucketed=False):
+def infer_stream(net, converter, batches, detector=None, segm_thresh=0.5, bucketed=False, native_preprocess=False):
     """`infer_batch` over a SEQUENCE of batches with two batches in flight (a generator: one list of (boxes, texts) per
     batch, in order): the network pass of batch k + 1 is enqueued on the caller's stream BEFORE batch k's boxes are read
     back, and batch k's second half -- read-backs, host merges, RoIRotate, head, strings -- runs on a second stream
     beside it.  The device never waits for the host's merges and string building, the host never waits for a network
     pass it does not need yet; results are those of `infer_batch` (same kernels on the same data).  `detector`: a callable
     `(k, im_data) -> maps` (the batch's index first), or None.  `bucketed`: see `batched`; everything the bucketed op
-    allocates (crops, tables, scratch) is allocated on the side stream that uses it, so the invariant below covers it."""
+    allocates (crops, tables, scratch) is allocated on the side stream that uses it, so the invariant below covers it.
+    `native_preprocess`: see `infer_batch`; the packed upload and the input tensor are allocated, written and read on the
+    caller's stream alone (the side stream reads neither), so the invariant needs nothing more."""
     device = next(net.parameters()).device
     side = torch.cuda.Stream(device=device)
 
@@ -263,7 +399,8 @@ def infer_stream(net, converter, batches, detector=None, segm_thresh=0.5, bucket
                 prev = None
             yield []
             continue
-        front = _batch_front(net, ims, None if detector is None else (lambda x, k=k: detector(k, x)), segm_thresh)
+        front = _batch_front(net, ims, None if detector is None else (lambda x, k=k: detector(k, x)), segm_thresh,
+                             native_preprocess)
         ready = torch.cuda.Event()
         ready.record()
         if prev is not None:

@@ -254,6 +254,7 @@ EXPORTS = (
     "rroi_ocr_head_forward_hip", "rroi_ocr_head_plan", "rroi_act_maxpool2x1_forward_hip",
     "rroi_conv1x1_forward_hip", "rroi_conv1x1_plan",
     "rroi_conv2x3_forward_hip", "rroi_conv2x3_plan", "rroi_up_depthwise3x3_forward_hip",   # bound in remainder.py
+    "rroi_preprocess_forward_hip", "rroi_preprocess_plan",   # bound in preprocess.py
 )
 
 # What a call launches (rroi_align_forward_plan / rroi_align_backward_plan); the fields of rroi_align_plan.

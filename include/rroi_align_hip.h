@@ -897,6 +897,51 @@ int rroi_conv2x3_plan(int dtype, int batch_size, int in_channels, int out_channe
 int rroi_up_depthwise3x3_forward_hip(int dtype, const void* a, const void* weight, void* y, int batch_size, int channels,
                                      int in_height, int in_width, int out_height, int out_width, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * 14. Native preprocessing: the uploaded bytes of a whole batch of images to the network's input tensor in
+ *    ONE launch -- the half-pixel bilinear resize, `/ 128 - 1` and the rounding to the network's type that
+ *    fots_e2e.pipeline.preprocess runs as a chain of stock operators per image.  Opt-in from Python
+ *    (fots_e2e.pipeline.preprocess_batch, the pipeline's native_preprocess keyword).
+ *
+ *      src     one device buffer of bytes: the batch's images back to back, image n (H0_n, W0_n, 3) interleaved, the
+ *              channel order kept as it is
+ *      table   (N, 4) int32 on the device: {byte offset of image n in src, H0_n, W0_n, 0}.  Offsets need NO alignment
+ *              (3 * H0 * W0 is rarely a multiple of 4) and the source sizes may differ from image to image.  The rows
+ *              are TRUSTED, as ROI rows are: an offset or a size that points outside src is read out of bounds.
+ *      y       (N, 3, out_height, out_width) contiguous NCHW of `dtype` (fp32, bf16 or fp16)
+ *    Any sizes >= 1 on both sides.
+ *
+ *    Arithmetic -- the whole contract; every operation rounded to double, in this order.  Per axis with source extent n0
+ *    and output extent n:  n0 == n: i0 = i1 = i, l = 0 (the source is read as it is);  otherwise
+ *      s = max(0, (i + 0.5) * ((double)n0 / (double)n) - 0.5),  i0 = min((int)floor(s), n0 - 1),  i1 = min(i0 + 1, n0 - 1),
+ *      l = s - i0.
+ *    top = (1 - lx) * p[y0][x0] + lx * p[y0][x1], bot likewise on row y1, v = (1 - ly) * top + ly * bot,
+ *    out = (T)(float)(v / 128.0 - 1.0) ((float) alone for fp32): F.interpolate(mode="bilinear", align_corners=False)
+ *    followed by test.py:77-83's scaling, evaluated in double and rounded once.  Where no resize is needed the fp32
+ *    result is bit for bit the stock chain's (p / 128 - 1 is exact).
+ *
+ *    Returns 1 / 0 / -hipError.  0, before any launch: an unknown dtype, batch_size < 0, out_height or out_width below 1,
+ *    a y of 2^31 elements or more, a NULL src, table or y with batch_size > 0.  batch_size == 0 is 1 and launches nothing.
+ *    Each call enqueues one kernel on `stream`, uses no workspace, allocates nothing and can be captured into a HIP graph.
+ *    Any element-aligned y works: 16-byte stores are used where out_width is a multiple of columns_per_thread AND y is
+ *    16-byte aligned, element stores otherwise; every element of y is written once and nothing else is.  Arrived after
+ *    0.10.0 under the same version string: detect it by symbol.
+ * ------------------------------------------------------------------------- */
+typedef struct rroi_preprocess_plan_info {
+    int grid_x;              /* workgroups: ceil(items / block); 0 for batch_size == 0 */
+    int block;               /* threads per workgroup: 256, one item each */
+    int columns_per_thread;  /* consecutive output columns of an item, all three channels: 16 bytes' worth, 4 (fp32) or 8 */
+    int rows_per_thread;     /* consecutive output rows of an item: 1, 2 or 4 (grows while the grid keeps 1024 waves) */
+    int strips;              /* ceil(out_width / columns_per_thread) */
+    int bands;               /* ceil(out_height / rows_per_thread) */
+    int items;               /* batch_size * bands * strips */
+    int wide_store;          /* 1: out_width % columns_per_thread == 0, 16-byte stores for a 16-byte aligned y */
+} rroi_preprocess_plan_info;
+int rroi_preprocess_forward_hip(int dtype, const unsigned char* src, const int* table, void* y, int batch_size,
+                                int out_height, int out_width, void* stream);
+/* host only, no launch; 1, or 0 for arguments the call would refuse */
+int rroi_preprocess_plan(int dtype, int batch_size, int out_height, int out_width, rroi_preprocess_plan_info* plan);
+
 /* Bin centres only: geom (R, PH, PW, 2) = (bin_cx, bin_cy), 0 where the bin is
  * outside the ROI's pooled width (kernel.cu:86-107).  Diagnostic / test hook. */
 int rroi_align_bin_centres_hip(float spatial_scale, int num_rois, int height, int width,
@@ -929,7 +974,7 @@ int rroi_align_get_trig_recipe_hip(void);
  * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b, the depthwise
  * convolution of section 5, the InstanceNorm of section 6, its fused epilogues of section 6b, the heads and gate of section 7, the gated merge
  * of section 8, the dense 3x3 convolution of section 9, the recogniser's head and activation + pool of section 10 and the 1x1
- * convolution of section 11. */
+ * convolution of section 11, and the calls of sections 12 to 14. */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
