@@ -35,7 +35,8 @@
 // the matrix cores with the shortcut's BatchNorm folded in, bfloat16 / float16), rroi_conv2x3_kernels.h
 // (+ rroi_conv2x3_host.h: the recogniser's (2,3) convolution on the matrix cores, bfloat16 / float16),
 // rroi_updw_kernels.h (+ rroi_updw_host.h: the bilinear resize and the depthwise 3x3 behind it in one launch),
-// rroi_preprocess_kernels.h (+ rroi_preprocess_host.h: uint8 images to the network's input tensor in one launch).
+// rroi_preprocess_kernels.h (+ rroi_preprocess_host.h: uint8 images to the network's input tensor in one launch),
+// rroi_ctc_loss_kernels.h (+ rroi_ctc_loss_host.h: the CTC loss and its unscaled gradient in one launch).
 // Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
 // launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
@@ -75,6 +76,7 @@ namespace {
 #include "rroi_conv2x3_kernels.h"
 #include "rroi_updw_kernels.h"
 #include "rroi_preprocess_kernels.h"
+#include "rroi_ctc_loss_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
@@ -89,6 +91,7 @@ namespace {
 #include "rroi_conv2x3_host.h"
 #include "rroi_updw_host.h"
 #include "rroi_preprocess_host.h"
+#include "rroi_ctc_loss_host.h"
 
 }  // namespace
 
@@ -983,6 +986,44 @@ int rroi_preprocess_forward_hip(int dtype, const unsigned char* src, const int* 
     return with_dtype(dtype, [&](auto tag) {
         typedef decltype(tag) T;
         return launch_preprocess(P, src, table, static_cast<T*>(y), out_height, out_width, stream);
+    });
+}
+
+// ------------------------------------------------------------------------------------
+// The native CTC loss (header section 15): every sequence's nll and the unscaled gradient in one launch.
+// ------------------------------------------------------------------------------------
+int rroi_ctc_loss_plan(int dtype, int batch_size, int classes, int steps, int max_target_length, long long stride_t,
+                       long long stride_k, int want_grad, rroi_ctc_loss_plan_info* plan)
+{
+    const CtcPlan P = plan_ctc_loss(dtype, batch_size, classes, steps, max_target_length, stride_t, stride_k, want_grad);
+    if (!P.status || !plan) return 0;
+    *plan = rroi_ctc_loss_plan_info{(int)P.grid, kCtcThreads, (int)P.lds_bytes, (int)kCtcLdsLimit, P.smax, P.chunk, P.along_t,
+                                    P.workspace_bytes != 0};
+    return 1;
+}
+
+size_t rroi_ctc_loss_workspace_bytes(int batch_size, int classes, int steps, int max_target_length, int want_grad)
+{
+    return plan_ctc_loss(RROI_DTYPE_FP32, batch_size, classes, steps, max_target_length, 0, 1, want_grad).workspace_bytes;
+}
+
+int rroi_ctc_loss_forward_hip(int dtype, const void* log_probs, long long stride_t, long long stride_n, long long stride_k,
+                              int batch_size, int classes, int steps, const int* targets, int max_target_length,
+                              const int* input_lengths, const int* target_lengths, int blank, int zero_infinity, float* nll,
+                              void* grad, long long grad_stride_t, long long grad_stride_n, long long grad_stride_k,
+                              void* workspace, size_t workspace_bytes, void* stream_)
+{
+    const CtcPlan P = plan_ctc_loss(dtype, batch_size, classes, steps, max_target_length, stride_t, stride_k, grad != nullptr);
+    if (!P.status || blank < 0 || blank >= classes) return 0;
+    if (batch_size == 0) return 1;
+    if (!log_probs || !input_lengths || !target_lengths || !nll || (max_target_length > 0 && !targets)) return 0;
+    if (P.workspace_bytes && (!workspace || workspace_bytes < P.workspace_bytes || reinterpret_cast<size_t>(workspace) % 8)) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_ctc_loss(P, static_cast<const T*>(log_probs), CtcStrides{stride_t, stride_n, stride_k}, classes, steps, targets,
+                               max_target_length, input_lengths, target_lengths, blank, zero_infinity, nll, static_cast<T*>(grad),
+                               CtcStrides{grad_stride_t, grad_stride_n, grad_stride_k}, workspace, stream);
     });
 }
 

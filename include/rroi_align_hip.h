@@ -942,6 +942,67 @@ int rroi_preprocess_forward_hip(int dtype, const unsigned char* src, const int* 
 /* host only, no launch; 1, or 0 for arguments the call would refuse */
 int rroi_preprocess_plan(int dtype, int batch_size, int out_height, int out_width, rroi_preprocess_plan_info* plan);
 
+/* ------------------------------------------------------------------------- *
+ * 15. The native CTC loss: the negative log-likelihood of every sequence and, where wanted, its UNSCALED
+ *    gradient with respect to the log-probabilities, in ONE launch -- deterministic (no atomic, every sum in a fixed
+ *    order: the same bits on every run), for fp32, bf16 and fp16 log-probabilities read where they lie.  Opt-in from
+ *    Python (rroi_align.ctc.ctc_loss, fots_e2e.train.recognition_loss(native_ctc=True)).
+ *
+ *      log_probs        element (t, n, k) at log_probs[t * stride_t + n * stride_n + k * stride_k], t < steps, n < batch_size,
+ *                       k < classes; any element strides (loads and stores coalesce where stride_t or stride_k is 1)
+ *      targets          (batch_size, max_target_length) contiguous int32, row n holding target_lengths[n] labels
+ *      input_lengths    (batch_size) int32 on the device, T_n
+ *      target_lengths   (batch_size) int32 on the device, L_n
+ *      nll              (batch_size) float32
+ *      grad             NULL, or the gradient tensor with element strides of its own; every element (t, n, k) is written
+ *                       exactly once, zeros included, so the caller neither clears it nor reads it before
+ *      workspace        rroi_ctc_loss_workspace_bytes(...) bytes, 8-byte aligned (0 bytes: may be NULL)
+ *
+ *    Arithmetic -- the whole contract, every operation in double.  lp = log_probs widened exactly; l' = the target with
+ *    blanks interleaved, S = 2 L + 1; lse(...) = m + log(sum of exp(x - m)), m the largest argument, -inf where m is:
+ *      alpha_0(0) = lp[blank, 0], alpha_0(1) = lp[l_1, 0], -inf elsewhere
+ *      alpha_t(s) = lp[l'_s, t] + lse(alpha_{t-1}(s), alpha_{t-1}(s-1), [alpha_{t-1}(s-2) if l'_s != blank and != l'_{s-2}])
+ *      nll_n      = -lse(alpha_{T_n-1}(S-1), alpha_{T_n-1}(S-2)); T_n == 0: 0 if L_n == 0, else +inf
+ *      beta the mirror image;  for t < T_n, with lp[k, t] and nll_n finite,
+ *      grad[t, n, k] = exp(lp) - exp(lse_{s : l'_s = k}(alpha_t(s) + beta_t(s)) + nll_n - lp)
+ *    -- torch.nn.functional.ctc_loss's gradient for grad_output = 1.  The gradient is 0 for t >= T_n, 0 where lp is -inf,
+ *    and 0 for a sequence whose nll is +inf (torch leaves NaN in the last two cases).  nll is rounded to float32, the
+ *    gradient once from double to `dtype`.  With zero_infinity an infinite nll is stored as 0.
+ *    A sequence is INFEASIBLE -- nll +inf, gradient 0 -- where T_n is outside [0, steps], L_n outside
+ *    [0, min(max_target_length, steps)], or one of its L_n labels outside [0, classes).  This is decided before anything is
+ *    read through a length or a label: no contents of the three integer tensors make the call read or write out of bounds.
+ *
+ *    Returns 1 / 0 / -hipError.  0, before any launch: an unknown dtype, batch_size, steps or max_target_length below 0,
+ *    classes below 1, blank outside [0, classes), a shape whose per-sequence arrays exceed the 64 KiB of LDS the kernel may
+ *    use even at one step per chunk (60 * S_max + 8 * classes + 4 bytes, S_max = 2 * min(max_target_length, steps) + 1), a NULL log_probs, input_lengths, target_lengths
+ *    or nll -- or targets with max_target_length > 0 -- with batch_size > 0, a workspace that is needed and NULL, short or
+ *    not 8-byte aligned.  batch_size == 0 is 1 and launches nothing.  Each call enqueues one kernel on `stream`, allocates
+ *    nothing and can be captured into a HIP graph.  Arrived after 0.10.0 under the same version string: detect it by symbol.
+ * ------------------------------------------------------------------------- */
+typedef struct rroi_ctc_loss_plan_info {
+    int grid_x;              /* workgroups: one per sequence */
+    int block;               /* threads per workgroup: 256; thread s owns position s of l' */
+    int lds_bytes;           /* dynamic LDS of the launch, <= lds_limit */
+    int lds_limit;           /* 65536 */
+    int positions;           /* S_max = 2 * min(max_target_length, steps) + 1 */
+    int chunk_steps;         /* time steps staged, and gradient rows stored, at a time: 16, halved while the chunk's arrays
+                                (chunk_steps * (2 * positions + classes) doubles) exceed half of lds_limit */
+    int stage_along_t;       /* 1: log_probs is staged with consecutive lanes along t (stride_t == 1, stride_k != 1); 0: along
+                                positions / classes.  The gradient's stores choose likewise by the gradient's own strides. */
+    int alpha_in_workspace;  /* with a gradient: 0 = every alpha and beta row is kept in LDS, 1 = in the workspace (2 * T * S_max
+                                doubles per sequence did not fit); 0 without a gradient, which keeps two rows only */
+} rroi_ctc_loss_plan_info;
+int rroi_ctc_loss_forward_hip(int dtype, const void* log_probs, long long stride_t, long long stride_n, long long stride_k,
+                              int batch_size, int classes, int steps, const int* targets, int max_target_length,
+                              const int* input_lengths, const int* target_lengths, int blank, int zero_infinity, float* nll,
+                              void* grad, long long grad_stride_t, long long grad_stride_n, long long grad_stride_k,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* host only, no launch; 1, or 0 for arguments the call would refuse.  want_grad: whether the call passes a gradient. */
+int rroi_ctc_loss_plan(int dtype, int batch_size, int classes, int steps, int max_target_length, long long stride_t,
+                       long long stride_k, int want_grad, rroi_ctc_loss_plan_info* plan);
+/* host only: bytes of workspace the call needs (0: none; also 0 for arguments the call would refuse) */
+size_t rroi_ctc_loss_workspace_bytes(int batch_size, int classes, int steps, int max_target_length, int want_grad);
+
 /* Bin centres only: geom (R, PH, PW, 2) = (bin_cx, bin_cy), 0 where the bin is
  * outside the ROI's pooled width (kernel.cu:86-107).  Diagnostic / test hook. */
 int rroi_align_bin_centres_hip(float spatial_scale, int num_rois, int height, int width,
@@ -974,7 +1035,7 @@ int rroi_align_get_trig_recipe_hip(void);
  * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b, the depthwise
  * convolution of section 5, the InstanceNorm of section 6, its fused epilogues of section 6b, the heads and gate of section 7, the gated merge
  * of section 8, the dense 3x3 convolution of section 9, the recogniser's head and activation + pool of section 10 and the 1x1
- * convolution of section 11, and the calls of sections 12 to 14. */
+ * convolution of section 11, and the calls of sections 12 to 15. */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
