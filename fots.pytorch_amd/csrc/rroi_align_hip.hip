@@ -36,7 +36,8 @@
 // (+ rroi_conv2x3_host.h: the recogniser's (2,3) convolution on the matrix cores, bfloat16 / float16),
 // rroi_updw_kernels.h (+ rroi_updw_host.h: the bilinear resize and the depthwise 3x3 behind it in one launch),
 // rroi_preprocess_kernels.h (+ rroi_preprocess_host.h: uint8 images to the network's input tensor in one launch),
-// rroi_ctc_loss_kernels.h (+ rroi_ctc_loss_host.h: the CTC loss and its unscaled gradient in one launch).
+// rroi_ctc_loss_kernels.h (+ rroi_ctc_loss_host.h: the CTC loss and its unscaled gradient in one launch),
+// rroi_detection_loss_kernels.h (+ rroi_detection_loss_host.h: the detection loss and its gradient).
 // Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
 // launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
@@ -77,6 +78,7 @@ namespace {
 #include "rroi_updw_kernels.h"
 #include "rroi_preprocess_kernels.h"
 #include "rroi_ctc_loss_kernels.h"
+#include "rroi_detection_loss_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
@@ -92,6 +94,7 @@ namespace {
 #include "rroi_updw_host.h"
 #include "rroi_preprocess_host.h"
 #include "rroi_ctc_loss_host.h"
+#include "rroi_detection_loss_host.h"
 
 }  // namespace
 
@@ -1024,6 +1027,67 @@ int rroi_ctc_loss_forward_hip(int dtype, const void* log_probs, long long stride
         return launch_ctc_loss(P, static_cast<const T*>(log_probs), CtcStrides{stride_t, stride_n, stride_k}, classes, steps, targets,
                                max_target_length, input_lengths, target_lengths, blank, zero_infinity, nll, static_cast<T*>(grad),
                                CtcStrides{grad_stride_t, grad_stride_n, grad_stride_k}, workspace, stream);
+    });
+}
+
+// ------------------------------------------------------------------------------------
+// The native detection loss (header section 16): two launches forward (partial sums, finish), one backward.
+// ------------------------------------------------------------------------------------
+int rroi_detection_loss_plan(int dtype, int batch_size, int height, int width, int height8, int width8,
+                             rroi_detection_loss_plan_info* plan)
+{
+    const DlPlan P = plan_detection_loss(dtype, batch_size, height, width, height8, width8);
+    if (!P.status || !plan) return 0;
+    *plan = rroi_detection_loss_plan_info{(int)P.grid, kDlThreads, P.S.ipt, (int)P.S.blocks4, (int)P.S.blocks8, kDlSums, 2 * kDlSums,
+                                          kDlFinishThreads};
+    return 1;
+}
+
+size_t rroi_detection_loss_workspace_bytes(int batch_size, int height, int width, int height8, int width8)
+{
+    return plan_detection_loss(RROI_DTYPE_FP32, batch_size, height, width, height8, width8).workspace_bytes;
+}
+
+int rroi_detection_loss_forward_hip(int dtype, const void* segm4, const void* angle4, const void* roi4, const void* segm8,
+                                    const void* angle8, const void* roi8, const float* segm_gt, const float* iou_mask,
+                                    const float* angle_gt, const float* roi_gt, int batch_size, int height, int width, int height8,
+                                    int width8, float* terms, void* workspace, size_t workspace_bytes, void* stream_)
+{
+    const DlPlan P = plan_detection_loss(dtype, batch_size, height, width, height8, width8);
+    if (!P.status) return 0;
+    if (!segm4 || !angle4 || !roi4 || !segm_gt || !iou_mask || !angle_gt || !roi_gt || !terms) return 0;
+    if (height8 && (!segm8 || !angle8 || !roi8)) return 0;
+    if (!dl_aligned(roi_gt, 16)) return 0;                                        // read four channels at a time
+    if (!workspace || workspace_bytes < P.workspace_bytes || !dl_aligned(workspace, 8)) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        const DlPreds<T> p4{static_cast<const T*>(segm4), static_cast<const T*>(angle4), static_cast<const T*>(roi4)};
+        const DlPreds<T> p8{static_cast<const T*>(segm8), static_cast<const T*>(angle8), static_cast<const T*>(roi8)};
+        return launch_detection_loss_forward(P, p4, p8, DlTruth{segm_gt, iou_mask, angle_gt, roi_gt}, terms, workspace, stream);
+    });
+}
+
+int rroi_detection_loss_backward_hip(int dtype, const void* angle4, const void* roi4, const void* angle8, const void* roi8,
+                                     const float* segm_gt, const float* iou_mask, const float* angle_gt, const float* roi_gt,
+                                     int batch_size, int height, int width, int height8, int width8, const double* state,
+                                     const float* grad_terms, void* grad_segm4, void* grad_angle4, void* grad_roi4, void* grad_segm8,
+                                     void* grad_angle8, void* grad_roi8, void* stream_)
+{
+    const DlPlan P = plan_detection_loss(dtype, batch_size, height, width, height8, width8);
+    if (!P.status) return 0;
+    if (!angle4 || !roi4 || !segm_gt || !iou_mask || !angle_gt || !roi_gt || !grad_segm4 || !grad_angle4 || !grad_roi4) return 0;
+    if (height8 && (!angle8 || !roi8 || !grad_segm8 || !grad_angle8 || !grad_roi8)) return 0;
+    if (!dl_aligned(roi_gt, 16)) return 0;
+    if (!state || !dl_aligned(state, 8) || !grad_terms || !dl_aligned(grad_terms, 4)) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        const DlPreds<T> p4{nullptr, static_cast<const T*>(angle4), static_cast<const T*>(roi4)};
+        const DlPreds<T> p8{nullptr, static_cast<const T*>(angle8), static_cast<const T*>(roi8)};
+        const DlGrads<T> g4{static_cast<T*>(grad_segm4), static_cast<T*>(grad_angle4), static_cast<T*>(grad_roi4)};
+        const DlGrads<T> g8{static_cast<T*>(grad_segm8), static_cast<T*>(grad_angle8), static_cast<T*>(grad_roi8)};
+        return launch_detection_loss_backward(P, p4, p8, DlTruth{segm_gt, iou_mask, angle_gt, roi_gt}, state, grad_terms, g4, g8, stream);
     });
 }
 

@@ -14,7 +14,7 @@ Layout (all at the strides the reference uses):
             and on the 1/8 map (:438-457);
   recogniser `forward_ocr` (:334-379): conv5 .. conv11 with two (2,1) max-pools, log-softmax
             over classes, output (N, nclass, T) with T = pooled width.
-Only inference is restated (no losses, no weight recomputation hooks).
+Only the network is restated (no weight recomputation hooks); its two losses are in fots_e2e.train.
 """
 import torch
 import torch.nn as nn

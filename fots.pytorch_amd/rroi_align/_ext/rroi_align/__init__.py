@@ -256,6 +256,8 @@ EXPORTS = (
     "rroi_conv2x3_forward_hip", "rroi_conv2x3_plan", "rroi_up_depthwise3x3_forward_hip",   # bound in remainder.py
     "rroi_preprocess_forward_hip", "rroi_preprocess_plan",   # bound in preprocess.py
     "rroi_ctc_loss_forward_hip", "rroi_ctc_loss_plan", "rroi_ctc_loss_workspace_bytes",   # bound in ctc_loss.py
+    "rroi_detection_loss_forward_hip", "rroi_detection_loss_backward_hip", "rroi_detection_loss_plan",
+    "rroi_detection_loss_workspace_bytes",   # bound in detection_loss.py
 )
 
 # What a call launches (rroi_align_forward_plan / rroi_align_backward_plan); the fields of rroi_align_plan.

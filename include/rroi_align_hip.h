@@ -1003,6 +1003,83 @@ int rroi_ctc_loss_plan(int dtype, int batch_size, int classes, int steps, int ma
 /* host only: bytes of workspace the call needs (0: none; also 0 for arguments the call would refuse) */
 size_t rroi_ctc_loss_workspace_bytes(int batch_size, int classes, int steps, int max_target_length, int want_grad);
 
+/* ------------------------------------------------------------------------- *
+ * 16. The native detection loss: the reference's ModelResNetSep2.loss -- a dice term on the score maps, a
+ *    masked mean-squared error on the angle maps, an IoU term on the left and right halves of the boxes, on the 1/4 scale
+ *    and on the 1/8 scale -- and its gradient with respect to the six predictions.  Forward is two launches (partial sums,
+ *    finish), backward one; no host synchronisation, no atomic, every sum in a fixed order that depends on the shape alone:
+ *    the same bits on every run and on every device.  Opt-in from Python (rroi_align.detection.detection_loss,
+ *    fots_e2e.train.detection_loss(native=True)).
+ *
+ *      segm4, angle4, roi4   (N, 1, H, W), (N, 2, H, W), (N, 4, H, W) contiguous, of `dtype` (fp32, bf16, fp16)
+ *      segm8, angle8, roi8   the same at (H8, W8), any H8, W8 >= 1; all NULL with height8 == width8 == 0 (a single scale)
+ *      segm_gt, iou_mask, angle_gt   (N, H, W) contiguous float32
+ *      roi_gt                (N, H, W, 4) contiguous float32 {top, bottom, left, right}, 16-byte aligned
+ *      terms                 4 float32: {segm, angle, box, total}
+ *      workspace             rroi_detection_loss_workspace_bytes(...) bytes, 8-byte aligned: grid_x slots of 10 doubles,
+ *                            then the STATE of 20 doubles, which the backward call reads (pass workspace + 80 * grid_x bytes,
+ *                            or a copy of those 160 bytes)
+ *      grad_terms            4 float32 on the device: the gradient arriving at `terms`; read by the kernel, never by the host
+ *      grad_*                the six gradients, shaped and typed like the predictions; every element is written exactly
+ *                            once, zeros included, so the caller neither clears them nor reads them before
+ *
+ *    Arithmetic -- the whole contract, every operation in double, predictions widened exactly.  Per scale and pixel:
+ *      1/4:  g = segm_gt, m = iou_mask, th = angle_gt, (d1, d2, d3, d4) = roi_gt, as they lie
+ *      1/8:  each of the seven planes resized to (H8, W8), bilinear with align_corners = true by section 8's recipe --
+ *            s = (in - 1) / (out - 1) (0 where out == 1), src = s * dst, i0 = min((int)src, in - 1), i1 = min(i0 + 1, in - 1),
+ *            l1 = src - i0, l0 = 1 - l1, value = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11) -- and the four
+ *            roi planes then halved; nothing resized is ever stored
+ *      mask = g > 0.5 (of the double value);  p, (a0, a1), (r1, r2, r3, r4) the predictions
+ *      I = sum (p m)(g m),  P = sum p m,  G = sum g m;                          dice = -(2 I + 1) / (P + G + 1)
+ *      over mask: c = count, Ss = sum (a0 - sin th)^2, Sc = sum (a1 - cos th)^2;  angle = Ss / c + Sc / c
+ *      over mask and d3 > 0:  X = min(d3, r3) (min(d1, r1) + min(d2, r2)),  U = (d1 + d2) d3 + (r1 + r2) r3 - X,
+ *            Ll = sum -log((X + 1) / (U + 1)), nl = count;  likewise Lr, nr with d4, r4 over mask and d4 > 0
+ *      box = Ll / nl + Lr / nr
+ *      segm = dice4 + dice8, angle = angle4 + angle8, box = box4 + box8, total = segm + 2 angle + 0.5 box, to float32.
+ *    A quotient whose count is 0 -- no pixel above 0.5, or none with d3 > 0 or d4 > 0 -- contributes 0 and a zero gradient
+ *    (the reference gives NaN for an empty left or right selection).
+ *    Summation order: thread t of workgroup b adds items (b' 256 ipt) + t, + 256, ... in ascending order (b' the workgroup's
+ *    index within its scale); the workgroup's sum is a butterfly over each wave's 64 lanes (offsets 1, 2, ..., 32), then waves
+ *    0..3 in ascending order; the finish adds the slots of a scale in ascending order.
+ *    Gradient, for grad_terms = g: w_segm = g[0] + g[3], w_angle = g[1] + 2 g[3], w_box = g[2] + 0.5 g[3];
+ *      d/dp = w_segm (m (2 I + 1) / (P + G + 1)^2 - g m m 2 / (P + G + 1))
+ *      d/da0 = (2 w_angle / c)(a0 - sin th) on the mask, d/da1 with cos; 0 off it
+ *      d/dr: from L = log(U + 1) - log(X + 1), with min's gradient going to the smaller side and a tie split in half
+ *            (torch's rule), each half scaled by w_box / nl or w_box / nr; 0 off the mask
+ *    each rounded once from double to `dtype` (the 16-bit types through a float rounded to odd, as in section 15).
+ *    Nothing is indexed by a value read from a tensor: no contents of the ground truth take a kernel out of bounds.
+ *
+ *    Returns 1 / 0 / -hipError.  0, before any launch: an unknown dtype, batch_size, height or width below 1, height8 or
+ *    width8 below 0 or only one of them 0, more than 2^30 pixels on a scale, a NULL tensor that the shape needs, roi_gt not
+ *    16-byte aligned, a workspace that is NULL, short or not 8-byte aligned, a NULL or misaligned state or grad_terms.
+ *    The calls allocate nothing and can be captured into a HIP graph.  Arrived after 0.10.0 under the same version string:
+ *    detect it by symbol.
+ * ------------------------------------------------------------------------- */
+typedef struct rroi_detection_loss_plan_info {
+    int grid_x;              /* workgroups of the partial-sum launch and of the backward launch: blocks_quarter + blocks_eighth */
+    int block;               /* threads per workgroup: 256 */
+    int items_per_thread;    /* 1 up to 4096 items (pixels of both scales), 2 up to 16384, 4 up to 262144, 8 beyond */
+    int blocks_quarter;      /* ceil(N H W / (block * items_per_thread)): the workgroups of the 1/4 scale, which come first */
+    int blocks_eighth;       /* ceil(N H8 W8 / (block * items_per_thread)); 0 for a single scale */
+    int slot_doubles;        /* doubles a workgroup writes to its slot of the workspace: 10 */
+    int state_doubles;       /* doubles of the state behind the slots: 20 */
+    int finish_block;        /* threads of the one finishing workgroup: 64 */
+} rroi_detection_loss_plan_info;
+int rroi_detection_loss_forward_hip(int dtype, const void* segm4, const void* angle4, const void* roi4, const void* segm8,
+                                    const void* angle8, const void* roi8, const float* segm_gt, const float* iou_mask,
+                                    const float* angle_gt, const float* roi_gt, int batch_size, int height, int width, int height8,
+                                    int width8, float* terms, void* workspace, size_t workspace_bytes, void* stream);
+int rroi_detection_loss_backward_hip(int dtype, const void* angle4, const void* roi4, const void* angle8, const void* roi8,
+                                     const float* segm_gt, const float* iou_mask, const float* angle_gt, const float* roi_gt,
+                                     int batch_size, int height, int width, int height8, int width8, const double* state,
+                                     const float* grad_terms, void* grad_segm4, void* grad_angle4, void* grad_roi4, void* grad_segm8,
+                                     void* grad_angle8, void* grad_roi8, void* stream);
+/* host only, no launch; 1, or 0 for arguments the calls would refuse.  A pure function of its arguments: never of the device. */
+int rroi_detection_loss_plan(int dtype, int batch_size, int height, int width, int height8, int width8,
+                             rroi_detection_loss_plan_info* plan);
+/* host only: bytes of workspace the forward call needs, (10 * grid_x + 20) * 8; 0 for arguments the calls would refuse */
+size_t rroi_detection_loss_workspace_bytes(int batch_size, int height, int width, int height8, int width8);
+
 /* Bin centres only: geom (R, PH, PW, 2) = (bin_cx, bin_cy), 0 where the bin is
  * outside the ROI's pooled width (kernel.cu:86-107).  Diagnostic / test hook. */
 int rroi_align_bin_centres_hip(float spatial_scale, int num_rois, int height, int width,
@@ -1035,7 +1112,7 @@ int rroi_align_get_trig_recipe_hip(void);
  * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b, the depthwise
  * convolution of section 5, the InstanceNorm of section 6, its fused epilogues of section 6b, the heads and gate of section 7, the gated merge
  * of section 8, the dense 3x3 convolution of section 9, the recogniser's head and activation + pool of section 10 and the 1x1
- * convolution of section 11, and the calls of sections 12 to 15. */
+ * convolution of section 11, and the calls of sections 12 to 16. */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
