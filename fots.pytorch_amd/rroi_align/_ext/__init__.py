@@ -1,1 +1,2 @@
-"""rroi_align._ext -- ctypes binding of librroi_align_hip.so (see rroi_align/__init__.py)."""
+"""rroi_align._ext -- ctypes binding of librroi_align_hip.so: the package `rroi_align`, one module per operator (see its
+__init__.py)."""

@@ -2,17 +2,16 @@
 log-likelihood of every sequence and the unscaled gradient with respect to the log-probabilities in one launch,
 deterministic, for float32 / bfloat16 / float16 log-probabilities read where they lie.
 
-A submodule of its own, as preprocess.py and remainder.py are: the package's `_*_run` callables are a closed list that the
-network's ledger test reads, so the hot call here is `run_ctc_loss`.  It shares the package's library handle, status check,
-stream, workspace and dtype table.  The public surface (argument forms, autograd, reductions) is rroi_align.ctc."""
+A module of the binding like the package's own (`csrc/rroi_ctc_loss_host.h`), loaded on first use by `rroi_align.ctc`: the
+package's `_*_run` callables are a closed list that the network's ledger test reads, so the hot call here is
+`run_ctc_loss`.  Its workspace is `_core`'s per-stream scratch, the one table of the process.  The public surface (argument
+forms, autograd, reductions) is rroi_align.ctc."""
 import collections
 import ctypes
 
 import torch
 
-from . import _check, _lib, _stream, _workspace, dtype_code, DTYPE_FP32, _DTYPES
-
-_i, _vp, _ll, _sz = ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_size_t
+from ._core import _DTYPES, DTYPE_FP32, _bind, _check, _i, _lib, _ll, _plan_query, _stream, _sz, _vp, _workspace, dtype_code
 
 
 class _CtcLossPlan(ctypes.Structure):
@@ -20,13 +19,10 @@ class _CtcLossPlan(ctypes.Structure):
                                   "alpha_in_workspace")]
 
 
-_lib.rroi_ctc_loss_forward_hip.restype = _i
-_lib.rroi_ctc_loss_forward_hip.argtypes = ([_i, _vp, _ll, _ll, _ll, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _ll, _ll, _ll,
-                                            _vp, _sz, _vp])
-_lib.rroi_ctc_loss_plan.restype = _i
-_lib.rroi_ctc_loss_plan.argtypes = [_i] * 5 + [_ll, _ll, _i, ctypes.POINTER(_CtcLossPlan)]
-_lib.rroi_ctc_loss_workspace_bytes.restype = _sz
-_lib.rroi_ctc_loss_workspace_bytes.argtypes = [_i] * 5
+_bind("rroi_ctc_loss_forward_hip", [_i, _vp, _ll, _ll, _ll, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _ll, _ll, _ll,
+                                    _vp, _sz, _vp])
+_bind("rroi_ctc_loss_plan", [_i] * 5 + [_ll, _ll, _i, ctypes.POINTER(_CtcLossPlan)])
+_bind("rroi_ctc_loss_workspace_bytes", [_i] * 5, _sz)
 
 CtcLossPlan = collections.namedtuple("CtcLossPlan", [n for n, _ in _CtcLossPlan._fields_])
 
@@ -40,11 +36,8 @@ def ctc_loss_plan(batch_size, classes, steps, max_target_length, stride_t=None, 
     refuse the arguments."""
     if stride_t is None:
         stride_t = int(batch_size) * int(classes)
-    p = _CtcLossPlan()
-    if _lib.rroi_ctc_loss_plan(dtype_code(dtype), int(batch_size), int(classes), int(steps), int(max_target_length),
-                               int(stride_t), int(stride_k), int(bool(want_grad)), ctypes.byref(p)) != 1:
-        raise ValueError("rroi_ctc_loss_plan: the call would refuse these arguments")
-    return CtcLossPlan(*(getattr(p, n) for n in CtcLossPlan._fields))
+    return _plan_query(_lib.rroi_ctc_loss_plan, _CtcLossPlan, CtcLossPlan, "rroi_ctc_loss_plan",
+                       (dtype_code(dtype), batch_size, classes, steps, max_target_length, stride_t, stride_k, bool(want_grad)))
 
 
 def ctc_loss_workspace_bytes(batch_size, classes, steps, max_target_length, want_grad=True) -> int:

@@ -2,17 +2,16 @@
 the dice, angle and IoU terms of both scales in two launches, their gradient with respect to the six predictions in one, no
 host synchronisation, deterministic, for float32 / bfloat16 / float16 predictions.
 
-A submodule of its own, as ctc_loss.py is: the package's `_*_run` callables are a closed list that the network's ledger
-test reads, so the hot calls here are `run_detection_loss` and `run_detection_loss_backward`.  The public surface (argument
-forms, checks, autograd) is rroi_align.detection."""
+A module of the binding like the package's own (`csrc/rroi_detection_loss_host.h`), loaded on first use by
+`rroi_align.detection`: the package's `_*_run` callables are a closed list that the network's ledger test reads, so the hot
+calls here are `run_detection_loss` and `run_detection_loss_backward`.  The public surface (argument forms, checks,
+autograd) is rroi_align.detection."""
 import collections
 import ctypes
 
 import torch
 
-from . import _check, _lib, _stream, dtype_code, DTYPE_FP32, _DTYPES
-
-_i, _vp, _sz = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
+from ._core import _DTYPES, DTYPE_FP32, _bind, _check, _i, _lib, _stream, _sz, _vp, dtype_code
 
 
 class _DetectionLossPlan(ctypes.Structure):
@@ -20,14 +19,10 @@ class _DetectionLossPlan(ctypes.Structure):
                                   "state_doubles", "finish_block")]
 
 
-_lib.rroi_detection_loss_forward_hip.restype = _i
-_lib.rroi_detection_loss_forward_hip.argtypes = [_i] + [_vp] * 10 + [_i] * 5 + [_vp, _vp, _sz, _vp]
-_lib.rroi_detection_loss_backward_hip.restype = _i
-_lib.rroi_detection_loss_backward_hip.argtypes = [_i] + [_vp] * 8 + [_i] * 5 + [_vp] * 9
-_lib.rroi_detection_loss_plan.restype = _i
-_lib.rroi_detection_loss_plan.argtypes = [_i] * 6 + [ctypes.POINTER(_DetectionLossPlan)]
-_lib.rroi_detection_loss_workspace_bytes.restype = _sz
-_lib.rroi_detection_loss_workspace_bytes.argtypes = [_i] * 5
+_bind("rroi_detection_loss_forward_hip", [_i] + [_vp] * 10 + [_i] * 5 + [_vp, _vp, _sz, _vp])
+_bind("rroi_detection_loss_backward_hip", [_i] + [_vp] * 8 + [_i] * 5 + [_vp] * 9)
+_bind("rroi_detection_loss_plan", [_i] * 6 + [ctypes.POINTER(_DetectionLossPlan)])
+_bind("rroi_detection_loss_workspace_bytes", [_i] * 5, _sz)
 
 DetectionLossPlan = collections.namedtuple("DetectionLossPlan", [n for n, _ in _DetectionLossPlan._fields_])
 

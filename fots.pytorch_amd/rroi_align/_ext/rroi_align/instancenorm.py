@@ -1,0 +1,146 @@
+"""rroi_align._ext.rroi_align.instancenorm -- the binding of the network's InstanceNorm2d with its activation (header
+section 6) and of the same with the residual add or the stem's mirror fused in (section 6b);
+`csrc/rroi_instancenorm_host.h`."""
+import collections
+import ctypes
+
+import torch
+
+from ._core import (_DTYPES, _IO_DTYPES, DTYPE_FP32, _bind, _check, _d, _f, _i, _lib, _plan_query, _require_cuda_f32, _stream, _sz, _vp,
+                    dtype_code)
+
+
+class _InormPlan(ctypes.Structure):
+    _fields_ = [(n, _i) for n in ("form", "launches", "segments", "segment_elems", "grid_x", "block", "vector_elems", "reserved")]
+
+
+_bind("rroi_instancenorm_forward_hip", [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _f, _vp, _sz, _vp])
+_bind("rroi_instancenorm_workspace_bytes", [_i] * 4, _sz)
+_bind("rroi_instancenorm_plan", [_i] * 5 + [ctypes.POINTER(_InormPlan)])
+_bind("rroi_instancenorm_fused_forward_hip", [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _f, _vp, _sz, _vp])
+INORM_PLANE, INORM_SPLIT = 1, 2
+
+InstanceNormPlan = collections.namedtuple("InstanceNormPlan", [n for n, _ in _InormPlan._fields_[:-1]])
+
+
+def instance_norm_plan(batch_size, channels, height, width, dtype=DTYPE_FP32) -> InstanceNormPlan:
+    """What `instance_norm` launches for a tensor of this shape (host only, no GPU needed: 256 CUs are assumed without
+    one): the form (INORM_PLANE / INORM_SPLIT), its launches, segments per plane, elements per segment, the grid.
+    ValueError where the call would refuse the arguments."""
+    return _plan_query(_lib.rroi_instancenorm_plan, _InormPlan, InstanceNormPlan, "rroi_instancenorm_plan",
+                       (dtype_code(dtype), batch_size, channels, height, width))
+
+
+def instance_norm_workspace_bytes(batch_size, channels, height, width) -> int:
+    """Bytes of workspace `rroi_instancenorm_forward_hip` needs for this shape: 0 in the plane form."""
+    return int(_lib.rroi_instancenorm_workspace_bytes(int(batch_size), int(channels), int(height), int(width)))
+
+
+def instance_norm(x: torch.Tensor, weight=None, bias=None, eps: float = 1e-5, negative_slope: float = 1.0) -> torch.Tensor:
+    """InstanceNorm2d of (N,C,H,W) `x` over each (n, c) plane (biased variance, instance statistics), then
+    `v < 0 ? v * negative_slope : v` (1.0: no activation, 0.0: ReLU) -- DESIGN 5.11.  float32, bfloat16 or float16;
+    weight and bias are (C,) of x's dtype, or both None.  x is made NCHW-contiguous.  Statistics in double, shifted by the
+    plane's first element; one rounding to fp32 and one to the tensor's type; the same bits on every run.  Forward only (no
+    autograd).  ValueError for mismatched shapes or dtypes, RuntimeError for CPU tensors."""
+    return instance_norm_fused(x, weight, bias, eps, negative_slope)      # its checks, in its order, and the plain call
+
+
+def _instance_norm_run(x: torch.Tensor, weight, bias, eps: float, negative_slope: float) -> torch.Tensor:
+    """The call itself, for arguments already checked (instance_norm above; fots_e2e.native after instancenorm_ok): x is a
+    contiguous CUDA (N,C,H,W) tensor, weight and bias contiguous (C,) of its dtype and device or both None.  Kept lean: a
+    network pass makes 49 of these calls and the one-image leg of the pipeline is bound by host time."""
+    index = x.device.index
+    if index != torch.cuda.current_device():
+        with torch.cuda.device(index):
+            return _instance_norm_run(x, weight, bias, eps, negative_slope)
+    out = torch.empty_like(x)
+    N, C, H, W = x.shape
+    if N == 0:
+        return out
+    nbytes = _lib.rroi_instancenorm_workspace_bytes(N, C, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    st = _lib.rroi_instancenorm_forward_hip(_DTYPES[x.dtype], x.data_ptr(), None if weight is None else weight.data_ptr(),
+                                            None if bias is None else bias.data_ptr(), out.data_ptr(), N, C, H, W, eps,
+                                            negative_slope, None if ws is None else ws.data_ptr(), nbytes, _stream())
+    if st != 1:
+        _check(st, "rroi_instancenorm_forward_hip")
+    return out
+
+
+def instance_norm_fused(x: torch.Tensor, weight=None, bias=None, eps: float = 1e-5, negative_slope: float = 1.0,
+                        residual=None, mirror: bool = False) -> torch.Tensor:
+    """`instance_norm` with an epilogue fused in -- DESIGN 5.13.
+    residual (x's shape, dtype and device):  act(instance_norm(x) + residual), the sum in fp32 and rounded once: the tail
+    of a residual block in one call.
+    mirror:  the InstanceNorm2d of `torch.cat((x, -x), 1)` with its activation, without the concatenation: (N,2C,H,W) from
+    (N,C,H,W); weight and bias are (2C,) or both None.  Not together with a residual.
+    With neither, `instance_norm`.  The same exceptions as `instance_norm`; ValueError also for a residual whose shape,
+    dtype or device is not x's, for mirror together with a residual, and for a weight that is not (2C,) under mirror."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a torch.Tensor")
+    if x.dim() != 4:
+        raise ValueError(f"x must be (N,C,H,W), got {tuple(x.shape)}")
+    if (weight is None) != (bias is None):
+        raise ValueError("weight and bias come together, or neither")
+    mirror = bool(mirror)
+    if mirror and residual is not None:
+        raise ValueError("mirror takes no residual")
+    features = x.size(1) * (2 if mirror else 1)
+    for name, p in (("weight", weight), ("bias", bias)):
+        if p is None:
+            continue
+        if not isinstance(p, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if tuple(p.shape) != (features,):
+            raise ValueError(f"{name} must be {(features,)} for x {tuple(x.shape)}{' mirrored' if mirror else ''}, "
+                             f"got {tuple(p.shape)}")
+        if p.dtype != x.dtype:
+            raise ValueError(f"x and {name} must have one dtype, got {x.dtype} and {p.dtype}")
+    if residual is not None:
+        if not isinstance(residual, torch.Tensor):
+            raise TypeError("residual must be a torch.Tensor")
+        if residual.shape != x.shape:
+            raise ValueError(f"residual must have x's shape {tuple(x.shape)}, got {tuple(residual.shape)}")
+        if residual.dtype != x.dtype:
+            raise ValueError(f"x and residual must have one dtype, got {x.dtype} and {residual.dtype}")
+        if residual.device != x.device:
+            raise ValueError("x and residual must be on the same device")
+    _require_cuda_f32(x, "x", _IO_DTYPES)
+    for name, p in (("weight", weight), ("bias", bias)):
+        if p is not None:
+            _require_cuda_f32(p, name, _IO_DTYPES)
+            if p.device != x.device:
+                raise ValueError(f"x and {name} must be on the same device")
+    if features < 1 or x.size(2) < 1 or x.size(3) < 1:
+        raise ValueError(f"x must have at least one channel, row and column, got {tuple(x.shape)}")
+    if mirror and 2 * x.numel() >= 1 << 31:
+        raise ValueError(f"the mirrored output of x {tuple(x.shape)} has 2^31 elements or more")
+    if weight is not None:
+        weight, bias = weight.contiguous(), bias.contiguous()
+    if residual is None and not mirror:
+        return _instance_norm_run(x.contiguous(), weight, bias, float(eps), float(negative_slope))
+    return _instance_norm_fused_run(x.contiguous(), weight, bias, float(eps), float(negative_slope),
+                                    None if residual is None else residual.contiguous(), mirror)
+
+
+def _instance_norm_fused_run(x: torch.Tensor, weight, bias, eps: float, negative_slope: float, residual, mirror: bool) -> torch.Tensor:
+    """The call itself, for arguments already checked (instance_norm_fused above; fots_e2e.native after fused_norm_ok): as
+    `_instance_norm_run`, with `residual` a contiguous tensor like x or None, and under `mirror` weight and bias (2C,) and
+    no residual.  Kept lean for the same reason."""
+    index = x.device.index
+    if index != torch.cuda.current_device():
+        with torch.cuda.device(index):
+            return _instance_norm_fused_run(x, weight, bias, eps, negative_slope, residual, mirror)
+    N, C, H, W = x.shape
+    out = torch.empty((N, 2 * C, H, W), dtype=x.dtype, device=x.device) if mirror else torch.empty_like(x)
+    if N == 0:
+        return out
+    nbytes = _lib.rroi_instancenorm_workspace_bytes(N, C, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    st = _lib.rroi_instancenorm_fused_forward_hip(
+        _DTYPES[x.dtype], x.data_ptr(), None if weight is None else weight.data_ptr(), None if bias is None else bias.data_ptr(),
+        None if residual is None else residual.data_ptr(), out.data_ptr(), N, C, H, W, 1 if mirror else 0, eps, negative_slope,
+        None if ws is None else ws.data_ptr(), nbytes, _stream())
+    if st != 1:
+        _check(st, "rroi_instancenorm_fused_forward_hip")
+    return out

@@ -1,17 +1,15 @@
 """rroi_align._ext.rroi_align.preprocess -- the binding of native preprocessing (header section 14): the
 uploaded bytes of a whole batch of uint8 images to the network's (N, 3, H, W) input tensor in one launch.
 
-A submodule of its own, as remainder.py is: the package's `_*_run` callables are a closed list that the network's ledger
-test reads, so the hot call here is `run_preprocess_images`.  It shares the package's library handle, status check, stream
-and dtype table."""
+A module of the binding like the package's own (`csrc/rroi_preprocess_host.h`), loaded on first use by `fots_e2e`: the
+package's `_*_run` callables are a closed list that the network's ledger test reads, so the hot call here is
+`run_preprocess_images`."""
 import collections
 import ctypes
 
 import torch
 
-from . import _check, _lib, _stream, dtype_code, DTYPE_FP32, _DTYPES, _IO_DTYPES, _require_cuda_f32
-
-_i, _vp = ctypes.c_int, ctypes.c_void_p
+from ._core import _DTYPES, _IO_DTYPES, DTYPE_FP32, _bind, _check, _i, _lib, _plan_query, _require_cuda_f32, _stream, _vp, dtype_code
 
 
 class _PreprocessPlan(ctypes.Structure):
@@ -19,10 +17,8 @@ class _PreprocessPlan(ctypes.Structure):
                                   "wide_store")]
 
 
-_lib.rroi_preprocess_forward_hip.restype = _i
-_lib.rroi_preprocess_forward_hip.argtypes = [_i, _vp, _vp, _vp, _i, _i, _i, _vp]
-_lib.rroi_preprocess_plan.restype = _i
-_lib.rroi_preprocess_plan.argtypes = [_i] * 4 + [ctypes.POINTER(_PreprocessPlan)]
+_bind("rroi_preprocess_forward_hip", [_i, _vp, _vp, _vp, _i, _i, _i, _vp])
+_bind("rroi_preprocess_plan", [_i] * 4 + [ctypes.POINTER(_PreprocessPlan)])
 
 PreprocessPlan = collections.namedtuple("PreprocessPlan", [n for n, _ in _PreprocessPlan._fields_])
 
@@ -32,10 +28,8 @@ def preprocess_plan(batch_size, height, width, dtype=DTYPE_FP32) -> PreprocessPl
     block, the columns and rows of one thread's item, the strips and bands, the item count and whether the 16-byte store
     form applies (it then runs where the result is 16-byte aligned).  ValueError where the call would refuse the
     arguments."""
-    p = _PreprocessPlan()
-    if _lib.rroi_preprocess_plan(dtype_code(dtype), int(batch_size), int(height), int(width), ctypes.byref(p)) != 1:
-        raise ValueError("rroi_preprocess_plan: the call would refuse these arguments")
-    return PreprocessPlan(*(getattr(p, n) for n in PreprocessPlan._fields))
+    return _plan_query(_lib.rroi_preprocess_plan, _PreprocessPlan, PreprocessPlan, "rroi_preprocess_plan",
+                       (dtype_code(dtype), batch_size, height, width))
 
 
 def preprocess_images(src_u8: torch.Tensor, table: torch.Tensor, size, dtype=torch.float32, out=None) -> torch.Tensor:

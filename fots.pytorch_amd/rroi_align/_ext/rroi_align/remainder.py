@@ -2,17 +2,16 @@
 16-bit pass of FOTSNet: the recogniser's (2,3) convolution on the matrix cores (header section 12) and the
 bilinear resize fused with the depthwise 3x3 behind it (header section 13).
 
-A submodule of its own: the package's `_*_run` callables are a closed list that the network's ledger test reads, so the
-hot calls here are `run_conv2x3` and `run_up_depthwise3x3`.  It shares the package's library handle, status check, stream
-and dtype table."""
+A module of the binding like the package's own (`csrc/rroi_conv2x3_host.h`, `rroi_updw_host.h`), loaded on first use by
+`fots_e2e`: the package's `_*_run` callables are a closed list that the network's ledger test reads, so the hot calls here
+are `run_conv2x3` and `run_up_depthwise3x3`."""
 import collections
 import ctypes
 
 import torch
 
-from . import _check, _lib, _stream, dtype_code, DTYPE_BF16, _CONV_DTYPES, _DTYPES, _IO_DTYPES, _require_cuda_f32
-
-_i, _f, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+from ._core import (_CONV_DTYPES, _DTYPES, DTYPE_BF16, _bind, _check, _f, _finite, _i, _lib, _plan_query, _require_cuda_f32,
+                    _require_depthwise_device, _require_depthwise_shapes, _require_out, _stream, _vp, dtype_code)
 
 
 class _Conv2x3Plan(ctypes.Structure):
@@ -20,12 +19,9 @@ class _Conv2x3Plan(ctypes.Structure):
                                   "grid_x", "block", "lds_bytes", "out_h", "out_w", "reserved")]
 
 
-_lib.rroi_conv2x3_forward_hip.restype = _i
-_lib.rroi_conv2x3_forward_hip.argtypes = [_i, _vp, _vp, _vp] + [_i] * 5 + [_f, _vp]
-_lib.rroi_conv2x3_plan.restype = _i
-_lib.rroi_conv2x3_plan.argtypes = [_i] * 6 + [ctypes.POINTER(_Conv2x3Plan)]
-_lib.rroi_up_depthwise3x3_forward_hip.restype = _i
-_lib.rroi_up_depthwise3x3_forward_hip.argtypes = [_i, _vp, _vp, _vp] + [_i] * 6 + [_vp]
+_bind("rroi_conv2x3_forward_hip", [_i, _vp, _vp, _vp] + [_i] * 5 + [_f, _vp])
+_bind("rroi_conv2x3_plan", [_i] * 6 + [ctypes.POINTER(_Conv2x3Plan)])
+_bind("rroi_up_depthwise3x3_forward_hip", [_i, _vp, _vp, _vp] + [_i] * 6 + [_vp])
 
 # --------------------------------------------------------------------------- the (2,3) convolution (header section 12)
 Conv2x3Plan = collections.namedtuple("Conv2x3Plan", [n for n, _ in _Conv2x3Plan._fields_[:-1]])
@@ -36,11 +32,8 @@ def conv2x3_plan(batch_size, in_channels, out_channels, height, width, dtype=DTY
     no GPU needed): the tile (output channels, columns), the items per workgroup, the K chunk and their number, the tiles
     along Cout and W, the item count, grid, block, LDS bytes and the output's size.  ValueError where the call would
     refuse the arguments (float32 and height < 2 among them)."""
-    p = _Conv2x3Plan()
-    if _lib.rroi_conv2x3_plan(dtype_code(dtype), int(batch_size), int(in_channels), int(out_channels), int(height), int(width),
-                              ctypes.byref(p)) != 1:
-        raise ValueError("rroi_conv2x3_plan: the call would refuse these arguments")
-    return Conv2x3Plan(*(getattr(p, n) for n in Conv2x3Plan._fields))
+    return _plan_query(_lib.rroi_conv2x3_plan, _Conv2x3Plan, Conv2x3Plan, "rroi_conv2x3_plan",
+                       (dtype_code(dtype), batch_size, in_channels, out_channels, height, width))
 
 
 def conv2x3(x: torch.Tensor, weight: torch.Tensor, negative_slope: float = 1.0, out=None) -> torch.Tensor:
@@ -59,9 +52,7 @@ def conv2x3(x: torch.Tensor, weight: torch.Tensor, negative_slope: float = 1.0, 
         raise ValueError(f"weight must be (Cout, {C}, 2, 3) for x {tuple(x.shape)}, got {tuple(weight.shape)}")
     if weight.dtype != x.dtype:
         raise ValueError(f"x and weight must have one dtype, got {x.dtype} and {weight.dtype}")
-    negative_slope = float(negative_slope)
-    if negative_slope != negative_slope or negative_slope in (float("inf"), float("-inf")):
-        raise ValueError(f"negative_slope must be finite, got {negative_slope!r}")
+    negative_slope = _finite(negative_slope, "negative_slope")
     _require_cuda_f32(x, "x", _CONV_DTYPES)
     _require_cuda_f32(weight, "weight", _CONV_DTYPES)
     if weight.device != x.device:
@@ -71,10 +62,7 @@ def conv2x3(x: torch.Tensor, weight: torch.Tensor, negative_slope: float = 1.0, 
     if not x.is_contiguous() or not weight.is_contiguous():
         raise ValueError("x and weight must be NCHW-contiguous")
     if out is not None:
-        shape = (N, weight.size(0), H - 1, W)
-        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != x.dtype or out.device != x.device
-                or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous {shape} tensor of x's dtype and device")
+        _require_out(out, (N, weight.size(0), H - 1, W), x)
     return run_conv2x3(x, weight, negative_slope, out)
 
 
@@ -105,28 +93,15 @@ def up_depthwise3x3(a: torch.Tensor, weight: torch.Tensor, size) -> torch.Tensor
     resized map is never stored.  float32, bfloat16 or float16, a and weight alike; a is made
     NCHW-contiguous.  Bit for bit what `depthwise3x3` gives on that rounded resized map; a source of the target's size is
     read as it is.  Forward only (no autograd).  ValueError for mismatched shapes or dtypes, RuntimeError for CPU tensors."""
-    if not isinstance(a, torch.Tensor) or not isinstance(weight, torch.Tensor):
-        raise TypeError("a and weight must be torch.Tensors")
-    if a.dim() != 4:
-        raise ValueError(f"a must be (N,C,h,w), got {tuple(a.shape)}")
-    N, C, h, w = a.shape
-    if tuple(weight.shape) != (C, 1, 3, 3):
-        raise ValueError(f"weight must be {(C, 1, 3, 3)} for a {tuple(a.shape)}, got {tuple(weight.shape)}")
-    if weight.dtype != a.dtype:
-        raise ValueError(f"a and weight must have one dtype, got {a.dtype} and {weight.dtype}")
+    _require_depthwise_shapes(a, weight, "a", "(N,C,h,w)")
     try:
         Ho, Wo = (int(v) for v in size)
     except (TypeError, ValueError):
         raise ValueError(f"size must be (Ho, Wo), got {size!r}") from None
     if Ho < 1 or Wo < 1:
         raise ValueError(f"size must be at least (1, 1), got {size!r}")
-    _require_cuda_f32(a, "a", _IO_DTYPES)
-    _require_cuda_f32(weight, "weight", _IO_DTYPES)
-    if weight.device != a.device:
-        raise ValueError("a and weight must be on the same device")
-    if C < 1 or h < 1 or w < 1:
-        raise ValueError(f"a must have at least one channel, row and column, got {tuple(a.shape)}")
-    if max(a.numel(), N * C * Ho * Wo) >= (1 << 31):
+    _require_depthwise_device(a, weight, "a")
+    if max(a.numel(), a.size(0) * a.size(1) * Ho * Wo) >= (1 << 31):
         raise ValueError("a and the result must each have fewer than 2^31 elements")
     return run_up_depthwise3x3(a.contiguous(), weight, (Ho, Wo))
 
