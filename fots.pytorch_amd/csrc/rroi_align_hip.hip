@@ -37,7 +37,9 @@
 // rroi_updw_kernels.h (+ rroi_updw_host.h: the bilinear resize and the depthwise 3x3 behind it in one launch),
 // rroi_preprocess_kernels.h (+ rroi_preprocess_host.h: uint8 images to the network's input tensor in one launch),
 // rroi_ctc_loss_kernels.h (+ rroi_ctc_loss_host.h: the CTC loss and its unscaled gradient in one launch),
-// rroi_detection_loss_kernels.h (+ rroi_detection_loss_host.h: the detection loss and its gradient).
+// rroi_detection_loss_kernels.h (+ rroi_detection_loss_host.h: the detection loss and its gradient),
+// rroi_instancenorm_backward_kernels.h (+ rroi_instancenorm_backward_host.h: the InstanceNorm's training forward and its
+// backward).
 // Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
 // launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
@@ -79,6 +81,7 @@ namespace {
 #include "rroi_preprocess_kernels.h"
 #include "rroi_ctc_loss_kernels.h"
 #include "rroi_detection_loss_kernels.h"
+#include "rroi_instancenorm_backward_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
@@ -95,6 +98,7 @@ namespace {
 #include "rroi_preprocess_host.h"
 #include "rroi_ctc_loss_host.h"
 #include "rroi_detection_loss_host.h"
+#include "rroi_instancenorm_backward_host.h"
 
 }  // namespace
 
@@ -645,6 +649,80 @@ int rroi_instancenorm_fused_forward_hip(int dtype, const void* x, const void* ga
                                                            (unsigned)channels, eps, negative_slope, workspace, stream);
         return launch_instancenorm_fused<T, kInResidual>(P, xt, g, bt, static_cast<const T*>(residual), static_cast<T*>(y),
                                                          (unsigned)channels, eps, negative_slope, workspace, stream);
+    });
+}
+
+// The training twin of the plain call (header section 6c): the same y, and the {mean, var} of every plane.
+int rroi_instancenorm_forward_train_hip(int dtype, const void* x, const void* gamma, const void* beta, void* y, void* stats,
+                                        int batch_size, int channels, int height, int width, double eps, float negative_slope,
+                                        void* workspace, size_t workspace_bytes, void* stream_)
+{
+    const InormPlan P = plan_instancenorm(dtype, batch_size, channels, height, width, num_cus());
+    if (!P.status) return 0;
+    if (!x || !y || !stats || (gamma == nullptr) != (beta == nullptr)) return 0;
+    if (!std::isfinite(eps) || !(eps > 0.0) || !std::isfinite(negative_slope)) return 0;
+    if (P.ws_bytes &&
+        (!workspace_ok(workspace) || workspace_bytes < rroi_instancenorm_workspace_bytes(batch_size, channels, height, width)))
+        return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_instancenorm_train(P, static_cast<const T*>(x), static_cast<const T*>(gamma), static_cast<const T*>(beta),
+                                         static_cast<T*>(y), static_cast<double2*>(stats), (unsigned)channels, eps,
+                                         negative_slope, workspace, stream);
+    });
+}
+
+size_t rroi_instancenorm_backward_workspace_bytes(int batch_size, int channels, int height, int width)
+{
+    size_t bytes = 0;   // no dtype, as the forward's query: what the largest of the three plans needs (today they are one)
+    for (const int dtype : {RROI_DTYPE_FP32, RROI_DTYPE_BF16, RROI_DTYPE_FP16})
+        bytes = std::max(bytes, plan_instancenorm_backward(dtype, batch_size, channels, height, width, num_cus()).ws_bytes);
+    return bytes;
+}
+
+int rroi_instancenorm_backward_plan(int dtype, int batch_size, int channels, int height, int width,
+                                    rroi_instancenorm_plan_info* plan)
+{
+    const InormPlan P = plan_instancenorm_backward(dtype, batch_size, channels, height, width, num_cus()).P;
+    if (!P.status || !plan) return 0;
+    // launches: of a call that wants every gradient (the parameter-gradient kernel is the last; one fewer without it)
+    *plan = rroi_instancenorm_plan_info{P.form, P.form == RROI_INORM_SPLIT ? 3 : 2, (int)P.nseg, (int)P.seg, (int)P.grid,
+                                        kInThreads, dtype == RROI_DTYPE_FP32 ? 4 : 8, 0};
+    return 1;
+}
+
+int rroi_instancenorm_backward_hip(int dtype, const void* dy, const void* x, const void* stats, const void* gamma,
+                                   const void* beta, void* dx, void* dgamma, void* dbeta, int batch_size, int channels,
+                                   int height, int width, double eps, float negative_slope, void* workspace,
+                                   size_t workspace_bytes, void* stream_)
+{
+    const InormBwdPlan B = plan_instancenorm_backward(dtype, batch_size, channels, height, width, num_cus());
+    if (!B.P.status) return 0;
+    if (!dy || !x || !stats || (gamma == nullptr) != (beta == nullptr) || (dgamma == nullptr) != (dbeta == nullptr)) return 0;
+    if (!dx && !dgamma) return 0;
+    if (dgamma && !gamma) return 0;
+    if (!std::isfinite(eps) || !(eps > 0.0) || !std::isfinite(negative_slope)) return 0;
+    if (dx) {
+        const size_t bytes = (size_t)B.P.planes * B.P.n * (dtype == RROI_DTYPE_FP32 ? 4 : 2);
+        const char* o = static_cast<const char*>(dx);
+        for (const void* in : {x, dy}) {
+            const char* i = static_cast<const char*>(in);
+            if (o < i + bytes && i < o + bytes) return 0;
+        }
+    }
+    if ((dgamma || B.P.form == RROI_INORM_SPLIT) &&
+        (!workspace_ok(workspace) ||
+         workspace_bytes < rroi_instancenorm_backward_workspace_bytes(batch_size, channels, height, width)))
+        return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_instancenorm_backward(B, static_cast<const T*>(dy), static_cast<const T*>(x),
+                                            static_cast<const double2*>(stats), static_cast<const T*>(gamma),
+                                            static_cast<const T*>(beta), static_cast<T*>(dx), static_cast<T*>(dgamma),
+                                            static_cast<T*>(dbeta), (unsigned)batch_size, (unsigned)channels, eps,
+                                            negative_slope, workspace, stream);
     });
 }
 

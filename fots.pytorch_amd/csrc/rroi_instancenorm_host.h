@@ -36,7 +36,9 @@ struct InormPlan {
     size_t ws_bytes = 0;       // one {s1, s2} pair of doubles per workgroup, split form only
 };
 
-inline InormPlan plan_instancenorm(int dtype, int batch_size, int channels, int height, int width, int cus)
+// the rule itself, for a threshold pair: the forward's (plan_instancenorm) or the backward's (rroi_instancenorm_backward_host.h)
+inline InormPlan plan_inorm_forms(int dtype, int batch_size, int channels, int height, int width, int cus, unsigned min_plane,
+                                  unsigned planes_per_cu)
 {
     InormPlan P;
     if (!dtype_ok(dtype)) return P;
@@ -49,7 +51,7 @@ inline InormPlan plan_instancenorm(int dtype, int batch_size, int channels, int 
     P.status = 1;
     P.planes = (unsigned)((long long)batch_size * channels);
     P.n = (unsigned)((long long)height * width);
-    if (P.planes >= (unsigned)cus * kInSplitPlanesPerCu || P.n < kInSplitMinPlane) {
+    if (P.planes >= (unsigned)cus * planes_per_cu || P.n < min_plane) {
         P.form = RROI_INORM_PLANE;
         P.seg = P.n;
         P.grid = std::min(P.planes, kInMaxPlaneGrid);
@@ -59,9 +61,14 @@ inline InormPlan plan_instancenorm(int dtype, int batch_size, int channels, int 
     const unsigned want = std::min(kInMaxSegs, (kInWgPerCu * (unsigned)cus + P.planes - 1) / P.planes);
     P.seg = std::max(kInMinSeg, ((P.n + want - 1) / want + kInSegQuantum - 1) / kInSegQuantum * kInSegQuantum);
     P.nseg = (P.n + P.seg - 1) / P.seg;
-    P.grid = P.planes * P.nseg;    // < cus * kInSplitPlanesPerCu * kInMaxSegs
+    P.grid = P.planes * P.nseg;    // < cus * planes_per_cu * kInMaxSegs
     P.ws_bytes = align_up((size_t)P.grid * sizeof(double2), 256);
     return P;
+}
+
+inline InormPlan plan_instancenorm(int dtype, int batch_size, int channels, int height, int width, int cus)
+{
+    return plan_inorm_forms(dtype, batch_size, channels, height, width, cus, kInSplitMinPlane, kInSplitPlanesPerCu);
 }
 
 template <class T>

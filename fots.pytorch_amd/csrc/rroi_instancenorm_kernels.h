@@ -110,17 +110,32 @@ __device__ __forceinline__ InSums in_block_sum(InSums s, double* lds)
     return r;
 }
 
+// the plane's mean and (clamped) variance from its shifted sums
+__device__ __forceinline__ void in_moments(InSums s, double K, unsigned n, double& mean, double& var)
+{
+    const double m = s.s1 / (double)n;
+    mean = K + m;
+    var = s.s2 / (double)n - m * m;
+    if (var < 0.0) var = 0.0;          // a comparison, not fmax: a NaN stays a NaN and takes the plane with it
+}
+
+// a and b of a plane of channel c from its mean and variance (the backward forms them again, from the saved pair)
+template <class T>
+__device__ __forceinline__ void in_affine(double mean, double var, const T* gamma, const T* beta, unsigned c, double eps,
+                                          double& a, double& b)
+{
+    const double g = gamma ? (double)to_f32(gamma[c]) : 1.0, bt = gamma ? (double)to_f32(beta[c]) : 0.0;
+    a = g / sqrt(var + eps);
+    b = bt - mean * a;
+}
+
 template <class T>
 __device__ __forceinline__ void in_coefficients(InSums s, double K, unsigned n, const T* gamma, const T* beta, unsigned c,
                                                 double eps, double& a, double& b)
 {
-    const double g = gamma ? (double)to_f32(gamma[c]) : 1.0, bt = gamma ? (double)to_f32(beta[c]) : 0.0;
-    const double m = s.s1 / (double)n;
-    const double mean = K + m;
-    double var = s.s2 / (double)n - m * m;
-    if (var < 0.0) var = 0.0;          // a comparison, not fmax: a NaN stays a NaN and takes the plane with it
-    a = g / sqrt(var + eps);
-    b = bt - mean * a;
+    double mean, var;
+    in_moments(s, K, n, mean, var);
+    in_affine<T>(mean, var, gamma, beta, c, eps, a, b);
 }
 
 template <class T>

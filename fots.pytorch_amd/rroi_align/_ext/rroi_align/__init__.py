@@ -39,8 +39,10 @@ from .bucketed import (_TABLES_MAX, _bucket_tables, _bucketed_stats, _BucketTabl
 from .callers import ctc_greedy_decode  # noqa: F401
 from .depthwise import _depthwise3x3_run, depthwise3x3  # noqa: F401
 from .instancenorm import (INORM_PLANE, INORM_SPLIT, InstanceNormPlan, _InormPlan, _instance_norm_fused_run,  # noqa: F401
-                           _instance_norm_run, instance_norm, instance_norm_fused, instance_norm_plan,
-                           instance_norm_workspace_bytes)
+                           _instance_norm_run, instance_norm, instance_norm_backward, instance_norm_backward_plan,
+                           instance_norm_backward_workspace_bytes, instance_norm_fused, instance_norm_plan,
+                           instance_norm_train, instance_norm_workspace_bytes, run_instance_norm_backward,
+                           run_instance_norm_train)
 from .heads import HeadsPlan, _gate_run, _heads_run, _HeadsPlan, _require_pointwise, gate, heads, heads_plan  # noqa: F401
 from .merge import MergePlan, _gated_merge_run, _MergePlan, gated_merge, merge_plan  # noqa: F401
 from .conv3x3 import Conv3x3Plan, _conv3x3_run, _ConvPlan, conv3x3, conv3x3_plan  # noqa: F401
@@ -74,4 +76,6 @@ EXPORTS = (
     "rroi_ctc_loss_forward_hip", "rroi_ctc_loss_plan", "rroi_ctc_loss_workspace_bytes",   # bound in ctc_loss.py
     "rroi_detection_loss_forward_hip", "rroi_detection_loss_backward_hip", "rroi_detection_loss_plan",
     "rroi_detection_loss_workspace_bytes",   # bound in detection_loss.py
+    "rroi_instancenorm_forward_train_hip", "rroi_instancenorm_backward_hip", "rroi_instancenorm_backward_workspace_bytes",
+    "rroi_instancenorm_backward_plan",   # bound in instancenorm.py
 )

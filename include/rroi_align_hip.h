@@ -589,6 +589,67 @@ int rroi_instancenorm_fused_forward_hip(int dtype, const void* x, const void* ga
                                         float negative_slope, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * 6c. The InstanceNorm of section 6 for training: a forward that also leaves every plane's statistics,
+ *    and the backward that uses them.  Opt-in from Python (rroi_align.norm.instance_norm,
+ *    fots_e2e.native_train.use_trainable_instancenorm).
+ *
+ *    rroi_instancenorm_forward_train_hip is the call of section 6 with one more output:
+ *      stats  (N * C) pairs of doubles {mean, var}, 16-byte aligned: the plane's statistics exactly as the forward formed
+ *             them, mean = K + m and var after the clamp
+ *    y has the bits rroi_instancenorm_forward_hip gives for the same arguments; the plan and the workspace are those of
+ *    section 6.  It refuses what section 6 refuses, and a NULL stats.
+ *
+ *    rroi_instancenorm_backward_hip:
+ *      dy, x  (N, C, H, W)  contiguous NCHW, element type `dtype`: the gradient of the output, the forward's input
+ *      stats  (N * C) pairs  what the training forward left for this x
+ *      gamma, beta  (C)     the forward's, or BOTH NULL
+ *      dx     (N, C, H, W)  the same type, or NULL (then dgamma must not be: the map pass is skipped)
+ *      dgamma, dbeta  (C)   the same type, or BOTH NULL; they need gamma
+ *      eps, negative_slope  the forward's
+ *    Arithmetic per plane of n = H * W elements, all in double, each operation rounded once (no contraction):
+ *      a = gamma / sqrt(var + eps),  b = beta - mean * a                 the forward's coefficients again
+ *      v = (float)((double)x * a + b);  d = v > 0 ? 1 : negative_slope;  g = dy * d
+ *                                    -- the sign decisions are the forward's own; torch's convention at 0
+ *      rs = 1 / sqrt(var + eps);  xh = (x - mean) * rs
+ *      t1 = sum g,  t2 = sum g * xh          in an order that depends on the argument list alone (no atomics; the
+ *                                            order changes with the form and with x mod 16 bytes)
+ *      dx = (T)(float)(A * ((g - t1 / n) - xh * (t2 / n))),  A = gamma * rs  (rs where gamma is NULL)
+ *      dbeta[c] = sum over n of t1(n, c),  dgamma[c] = sum over n of t2(n, c),  in n order, each rounded once from double
+ *      to `dtype` (the 16-bit types through a float rounded to odd, as in section 15)
+ *    Two identical calls give identical bits.  A NaN or +-inf in a plane of x or dy stays in that plane's dx and in its
+ *    channel's parameter gradients.  Any element-aligned dy, x and dx work; dx must not overlap x or dy.
+ *
+ *    Two forms by the rule of section 6 with the backward's own thresholds -- rroi_instancenorm_backward_plan reports the
+ *    choice in the struct of section 6 (launches: of a call that wants every gradient; the parameter-gradient kernel is
+ *    the last launch and is left out where dgamma is NULL):
+ *      RROI_INORM_PLANE  one workgroup per plane: the two sums, then the map while the plane is in L2
+ *      RROI_INORM_SPLIT  a partials launch, `segments` workgroups per plane leaving one {t1, t2} pair each, then an apply
+ *                        launch in which every workgroup adds its plane's pairs in one fixed order and maps its segment
+ *    The workspace -- rroi_instancenorm_backward_workspace_bytes(N, C, H, W) bytes, never 0 for a valid shape, at a
+ *    256-byte-aligned address -- holds one {t1, t2} pair per plane for the parameter gradients and the split form's
+ *    partials.  It is needed where dgamma is not NULL or the form is RROI_INORM_SPLIT; elsewhere NULL / 0 is accepted
+ *    and a buffer that is handed over is left alone.  Its contents before and after the call mean nothing.
+ *
+ *    Returns 1 / 0 / -hipError.  0, before any launch: everything section 6 refuses (y's part read for dx), a NULL dy, x
+ *    or stats, exactly one of dgamma / dbeta NULL, dx and dgamma both NULL, dgamma without gamma, dx overlapping x or dy,
+ *    and -- where the workspace is needed -- a NULL workspace, one that is not a multiple of 256, or workspace_bytes
+ *    below the size query's answer.  Both calls only enqueue on `stream`, allocate nothing and can be captured into a HIP
+ *    graph.  Arrived after 0.10.0 under the same version string: detect them by symbol.
+ * ------------------------------------------------------------------------- */
+int rroi_instancenorm_forward_train_hip(int dtype, const void* x, const void* gamma, const void* beta, void* y, void* stats,
+                                        int batch_size, int channels, int height, int width, double eps, float negative_slope,
+                                        void* workspace, size_t workspace_bytes, void* stream);
+int rroi_instancenorm_backward_hip(int dtype, const void* dy, const void* x, const void* stats, const void* gamma,
+                                   const void* beta, void* dx, void* dgamma, void* dbeta, int batch_size, int channels,
+                                   int height, int width, double eps, float negative_slope, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+/* host only; 0 for arguments the call would refuse */
+size_t rroi_instancenorm_backward_workspace_bytes(int batch_size, int channels, int height, int width);
+/* host only, no launch; 1, or 0 for arguments the call would refuse */
+int rroi_instancenorm_backward_plan(int dtype, int batch_size, int channels, int height, int width,
+                                    rroi_instancenorm_plan_info* plan);
+
+/* ------------------------------------------------------------------------- *
  * 7. The network's detection heads and attention gate: a 1x1 convolution with bias from many channels to
  *    7 outputs (heads: `act` 1, `rbox` 4, `angle` 2 of tools/models.py) or to 1 (gate: `conv_attenton`), with the
  *    elementwise chain behind it -- three sigmoids, the scalings, the angle's normalisation -- in ONE launch that reads
@@ -1110,7 +1171,7 @@ int rroi_align_get_trig_recipe_hip(void);
 /* Identification: "rroi_align_hip <version> gfx950" (0.7.0: per-call trig recipe, device-wide setter removed; 0.8.0: launcher scratch reused within a capture, table of 64, stats; 0.9.0: plan query; 0.10.0: bfloat16 / float16 tensors).
  * The typed callers' entry points (rroi_rbox_decode_typed_hip, rroi_ctc_greedy_decode_typed_hip) arrived after 0.10.0 under
  * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b, the depthwise
- * convolution of section 5, the InstanceNorm of section 6, its fused epilogues of section 6b, the heads and gate of section 7, the gated merge
+ * convolution of section 5, the InstanceNorm of section 6, its fused epilogues of section 6b, its training calls of section 6c, the heads and gate of section 7, the gated merge
  * of section 8, the dense 3x3 convolution of section 9, the recogniser's head and activation + pool of section 10 and the 1x1
  * convolution of section 11, and the calls of sections 12 to 16. */
 const char* rroi_align_hip_version(void);
