@@ -39,7 +39,8 @@
 // rroi_ctc_loss_kernels.h (+ rroi_ctc_loss_host.h: the CTC loss and its unscaled gradient in one launch),
 // rroi_detection_loss_kernels.h (+ rroi_detection_loss_host.h: the detection loss and its gradient),
 // rroi_instancenorm_backward_kernels.h (+ rroi_instancenorm_backward_host.h: the InstanceNorm's training forward and its
-// backward).
+// backward), rroi_depthwise_backward_kernels.h (+ rroi_depthwise_backward_host.h: the depthwise 3x3
+// convolution's input and weight gradients).
 // Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
 // launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
@@ -82,6 +83,7 @@ namespace {
 #include "rroi_ctc_loss_kernels.h"
 #include "rroi_detection_loss_kernels.h"
 #include "rroi_instancenorm_backward_kernels.h"
+#include "rroi_depthwise_backward_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
@@ -99,6 +101,7 @@ namespace {
 #include "rroi_ctc_loss_host.h"
 #include "rroi_detection_loss_host.h"
 #include "rroi_instancenorm_backward_host.h"
+#include "rroi_depthwise_backward_host.h"
 
 }  // namespace
 
@@ -578,6 +581,47 @@ int rroi_depthwise3x3_forward_hip(int dtype, const void* x, const void* weight, 
         typedef decltype(tag) T;
         return launch_depthwise3x3(static_cast<const T*>(x), static_cast<const T*>(weight), static_cast<T*>(y), batch_size,
                                    channels, height, width, stride, stream);
+    });
+}
+
+// The backward of that convolution (header section 5b): one launch for dx, two and a workspace for dweight.
+size_t rroi_depthwise3x3_backward_workspace_bytes(int batch_size, int channels, int height, int width, int stride)
+{
+    return plan_depthwise_backward(RROI_DTYPE_FP32, batch_size, channels, height, width, stride).ws_bytes;   // no dtype in the rule
+}
+
+int rroi_depthwise3x3_backward_plan(int dtype, int batch_size, int channels, int height, int width, int stride,
+                                    rroi_depthwise_backward_plan_info* plan)
+{
+    const DwBwdPlan P = plan_depthwise_backward(dtype, batch_size, channels, height, width, stride);
+    if (!P.status || !plan) return 0;
+    // launches: of a call that wants both gradients (dx alone is one, dweight alone two)
+    *plan = rroi_depthwise_backward_plan_info{P.band * stride, kDwCols * stride, (int)P.dx_grid, P.band, (int)P.nseg,
+                                              (int)P.dw_grid, 3, kDwThreads};
+    return 1;
+}
+
+int rroi_depthwise3x3_backward_hip(int dtype, const void* dy, const void* x, const void* weight, void* dx, void* dweight,
+                                   int batch_size, int channels, int height, int width, int stride, void* workspace,
+                                   size_t workspace_bytes, void* stream_)
+{
+    const DwBwdPlan P = plan_depthwise_backward(dtype, batch_size, channels, height, width, stride);
+    if (!P.status) return 0;
+    if (!dy || (!dx && !dweight) || (dx && !weight) || (dweight && !x)) return 0;
+    if (dx) {
+        const size_t esize = dtype == RROI_DTYPE_FP32 ? 4 : 2;
+        const size_t out_bytes = (size_t)P.planes * height * width * esize, dy_bytes = (size_t)P.planes * P.Ho * P.Wo * esize;
+        const char *o = static_cast<const char*>(dx), *g = static_cast<const char*>(dy), *i = static_cast<const char*>(x);
+        if (o < g + dy_bytes && g < o + out_bytes) return 0;
+        if (dweight && o < i + out_bytes && i < o + out_bytes) return 0;   // (x is read only for dweight)
+    }
+    if (dweight && (!workspace_ok(workspace) || workspace_bytes < P.ws_bytes)) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_depthwise3x3_backward(P, static_cast<const T*>(dy), static_cast<const T*>(x), static_cast<const T*>(weight),
+                                            static_cast<T*>(dx), static_cast<T*>(dweight), batch_size, channels, height, width,
+                                            stride, workspace, stream);
     });
 }
 

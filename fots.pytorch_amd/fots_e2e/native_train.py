@@ -1,4 +1,5 @@
-"""fots_e2e.native_train -- the first operator of FOTSNet that stays on the package's own kernels when a gradient is needed.
+"""fots_e2e.native_train -- the operators of FOTSNet that stay on the package's own kernels when a gradient is needed:
+InstanceNorm2d (below) and the depthwise 3x3 convolution (at the end of the file).
 
 Every switch of `fots_e2e.native` is inference only: a call that needs a gradient takes the stock path.  The most frequent
 operator of the network, InstanceNorm2d (49 calls per pass, instance statistics in training as in the reference), has a
@@ -10,6 +11,15 @@ the other switches: opt-in, only classes change, each call asks a pure predicate
 
 The residual and mirror epilogues of DESIGN 5.13, running statistics, channels-last inputs and a double backward keep the
 stock path when a gradient is needed.
+
+The second most frequent operator, the depthwise 3x3 convolution (22 calls per pass), has a native backward as well
+(DESIGN 5.25): `use_trainable_depthwise(net)` -- called after `native.use_native_depthwise` -- switches every
+`DepthwiseConv3x3` to `TrainableDepthwiseConv3x3`, which runs `rroi_align.conv`'s autograd function where a gradient is
+needed and `trainable_depthwise_ok` holds.  With `native_remainder.use_native_upconv` on, a call that needs a gradient
+already falls back to the block's modules one by one, so all 22 are reached; the fused resize + depthwise has no backward.
+Channels-last inputs and autocast keep the stock path; a double backward needs it too (the function is once
+differentiable, and whether a graph of the backward will be wanted is not known when the forward runs): switch back with
+`enable=False` for one.
 
 It lives in a module of its own for the reason `native_remainder` does: the `_*_slower` hooks of `fots_e2e.native` are a
 closed list that the network tests read."""
@@ -79,6 +89,69 @@ def use_trainable_instancenorm(net: nn.Module, enable: bool = True) -> int:
     is copied, no key of the state_dict moves, a `fused_slope` stays.  Returns the number of modules switched (52 for
     `FOTSNet()`)."""
     src, dst = (_nat.NativeInstanceNorm2d, TrainableInstanceNorm2d) if enable else (TrainableInstanceNorm2d, _nat.NativeInstanceNorm2d)
+    n = 0
+    for m in net.modules():
+        if type(m) is src:
+            m.__class__ = dst
+            n += 1
+    return n
+
+
+# --------------------------------------------------------------------------- depthwise 3x3 convolution, DESIGN 5.25
+_CONV = []
+
+
+def _conv():
+    """`rroi_align.conv`, loaded on first use, as `_norm`."""
+    if not _CONV:
+        from rroi_align import conv
+        _CONV.append(conv)
+    return _CONV[0]
+
+
+def trainable_depthwise_ok(m, x) -> bool:
+    """True where `m(x)` may run the native forward and backward when a gradient is needed: `native.native_ok`'s conditions
+    other than its gradient clause (asked with gradients off, so that there is one copy of them), and not a shape class
+    whose forward + backward measured slower (`_dw_backward_slower`).  Pure, no GPU needed to ask."""
+    with torch.no_grad():
+        return _nat.native_ok(m, x) and not _dw_backward_slower(x, m.stride[0])
+
+
+def _dw_backward_slower(x, stride) -> bool:
+    """The shape classes in which native forward + backward did not meet the bar of DESIGN 5.10 against autograd of the
+    stock convolution (profiles/native_depthwise_backward.md, microseconds per forward + backward, native / stock minimum,
+    two runs of 36 rows: the network's six shapes at one and eight images in three dtypes).  There is none: no row misses
+    in both runs.
+      One row misses in the first run and not in the second -- float32, 512 planes of 22 x 40 at N = 1: 180.2 / 125.1
+        (rounds from 69.7 to 183.9), then 65.7 / 133.8.  It is not a property of the shape: every small shape stands at
+        65-68 native against 126-134 stock, the floor of issuing a forward + backward from Python, and in both runs whole
+        rounds of some native leg take one or two such floors longer, on the host clock as between device events (first run
+        also float32 1 x 256 x 176 x 320: 132.8 against 1517.0, 1 x 256 x 44 x 80 at stride 2: 128.0 / 132.7, 8 x 512 x 22 x 40:
+        131.0 / 248.8; second run bfloat16 8 x 256 x 88 x 160: 139.0 / 1075.1), which loses only where the stock leg is at
+        its own floor.  A disturbance of the host's issue time, kept and reported as DESIGN 5.24 did for its like.
+    A row that misses in both runs becomes a class here, its thresholds halfway to the next measured row, as
+    `_inorm_backward_slower` does."""
+    return False
+
+
+class TrainableDepthwiseConv3x3(_nat.DepthwiseConv3x3):
+    """A `DepthwiseConv3x3` (same parameters, same `state_dict` keys) whose forward, where a gradient is needed and
+    `trainable_depthwise_ok(self, x)` holds, is `rroi_align.conv`'s autograd function: native forward, native input
+    gradient, native deterministic weight gradient."""
+
+    def forward(self, x):
+        w = self._parameters["weight"]
+        if (isinstance(x, torch.Tensor) and torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)
+                and trainable_depthwise_ok(self, x)):
+            return _conv()._Depthwise3x3.apply(x, w, self.stride[0])
+        return super().forward(x)
+
+
+def use_trainable_depthwise(net: nn.Module, enable: bool = True) -> int:
+    """Switch every `DepthwiseConv3x3` of `net` to `TrainableDepthwiseConv3x3` (enable=False: back), so call it after
+    `native.use_native_depthwise` and undo it before undoing that.  Only the class of a module changes: no parameter is
+    copied, no key of the state_dict moves.  Returns the number of modules switched (22 for `FOTSNet()`)."""
+    src, dst = (_nat.DepthwiseConv3x3, TrainableDepthwiseConv3x3) if enable else (TrainableDepthwiseConv3x3, _nat.DepthwiseConv3x3)
     n = 0
     for m in net.modules():
         if type(m) is src:

@@ -37,7 +37,8 @@ from .bucketed import (_TABLES_MAX, _bucket_tables, _bucketed_stats, _BucketTabl
                        _tables, backward_bucketed, backward_bucketed_plan, bucket_layout, crop_table, forward_bucketed,
                        forward_bucketed_plan)
 from .callers import ctc_greedy_decode  # noqa: F401
-from .depthwise import _depthwise3x3_run, depthwise3x3  # noqa: F401
+from .depthwise import (DepthwiseBackwardPlan, _depthwise3x3_run, _DwBwdPlan, depthwise3x3, depthwise3x3_backward,  # noqa: F401
+                        depthwise3x3_backward_plan, depthwise3x3_backward_workspace_bytes, run_depthwise3x3_backward)
 from .instancenorm import (INORM_PLANE, INORM_SPLIT, InstanceNormPlan, _InormPlan, _instance_norm_fused_run,  # noqa: F401
                            _instance_norm_run, instance_norm, instance_norm_backward, instance_norm_backward_plan,
                            instance_norm_backward_workspace_bytes, instance_norm_fused, instance_norm_plan,
@@ -78,4 +79,5 @@ EXPORTS = (
     "rroi_detection_loss_workspace_bytes",   # bound in detection_loss.py
     "rroi_instancenorm_forward_train_hip", "rroi_instancenorm_backward_hip", "rroi_instancenorm_backward_workspace_bytes",
     "rroi_instancenorm_backward_plan",   # bound in instancenorm.py
+    "rroi_depthwise3x3_backward_hip", "rroi_depthwise3x3_backward_workspace_bytes", "rroi_depthwise3x3_backward_plan",
 )

@@ -499,6 +499,69 @@ int rroi_depthwise3x3_forward_hip(int dtype, const void* x, const void* weight, 
                                   int height, int width, int stride, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * 5b. The backward of the depthwise 3x3 convolution of section 5: the gradient of its input, bit-exact,
+ *    and the gradient of its weight, deterministic.  Opt-in from Python (rroi_align.conv.depthwise3x3,
+ *    fots_e2e.native_train.use_trainable_depthwise).
+ *
+ *      dy      (N, C, Ho, Wo)  contiguous NCHW, element type `dtype`: the gradient of the output; Ho, Wo as in section 5
+ *      x       (N, C, H, W)    contiguous NCHW, the forward's input; read for dweight only
+ *      weight  (C, 1, 3, 3)    the forward's; read for dx only
+ *      dx      (N, C, H, W)    the same type, or NULL; EVERY element is written and nothing else is
+ *      dweight (C, 1, 3, 3)    the same type, or NULL (not both NULL)
+ *    batch_size, channels, height, width are x's, whichever outputs are wanted.  With dx NULL weight may be NULL; with
+ *    dweight NULL x and the workspace may be.
+ *
+ *    dx, fixed so that results compare as bits (s = stride):
+ *      acc = +0.0 (double); for ky = 2, 1, 0: for kx = 2, 1, 0 (this order: dy is visited in row-major order):
+ *          if (iy + 1 - ky) % s == 0 and (ix + 1 - kx) % s == 0:   oy = (iy + 1 - ky) / s, ox = (ix + 1 - kx) / s
+ *              acc = acc + (double)weight[c, 0, ky, kx] * (double)(0 <= oy < Ho and 0 <= ox < Wo ? dy[n, c, oy, ox] : +0.0)
+ *      dx[n, c, iy, ix] = (T)(float)acc
+ *    -- the rounding of section 5: to fp32 once, then one plain conversion.  A tap of the right parity whose dy lies
+ *    outside is weight * (+0.0), never skipped, as the padding of section 5 is: a non-finite weight therefore gives NaN
+ *    along the border -- the first and last row and column at stride 1; at stride 2 the last row where H is even and the
+ *    last column where W is even -- where the mathematical gradient is finite.  A NaN or +-inf in dy reaches exactly the dx
+ *    elements whose taps read it.
+ *
+ *    dweight, deterministic:
+ *      dweight[c, 0, ky, kx] = sum over n, oy, ox of (double)dy[n, c, oy, ox] *
+ *                              (double)(inside the image ? x[n, c, s * oy - 1 + ky, s * ox - 1 + kx] : +0.0)
+ *    -- every product exact in double, every sum in double in an order that depends on the argument list alone (no
+ *    atomics), no chain of additions longer than 8192 at any legal shape, one rounding from double to `dtype` (the 16-bit
+ *    types through a float rounded to odd, as in sections 15 and 6c).  Two identical calls give identical bits.  A NaN
+ *    or +-inf in a plane of dy or x stays in its channel's dweight.
+ *    Two launches: `segments` workgroups per (n, c) plane -- a workgroup never mixes planes -- leave nine doubles each in
+ *    the workspace, then one workgroup per channel adds its N * segments entries in (n, segment) order and rounds.
+ *    Needs rroi_depthwise3x3_backward_workspace_bytes(N, C, H, W, stride) bytes, never 0 for a valid shape, at a
+ *    256-byte-aligned address; the contents before and after the call mean nothing.  Where dweight is NULL the workspace
+ *    is not needed: NULL / 0 is accepted and a buffer that is handed over is left alone.
+ *
+ *    Any element-aligned dy, x and dx work (a view one element into an allocation is a legal argument).
+ *    Returns 1 / 0 / -hipError.  0, before any launch: everything section 5 refuses for (N, C, H, W, stride), a NULL dy, dx
+ *    and dweight both NULL, dx without weight, dweight without x, dx overlapping dy (or x, where dweight is wanted too), and
+ *    -- where dweight is wanted -- a NULL workspace, one that is not a multiple of 256, or workspace_bytes below the size
+ *    query's answer.  The call only enqueues on `stream`, allocates nothing and can be captured into a HIP graph.
+ *    Arrived after 0.10.0 under the same version string: detect it by symbol.
+ * ------------------------------------------------------------------------- */
+typedef struct rroi_depthwise_backward_plan_info {
+    int dx_band;        /* dx rows per thread of the dx launch: 2, 4 or 8 times the stride */
+    int dx_cols;        /* dx columns per thread: 4 (stride 1) / 8 (stride 2) */
+    int dx_grid_x;      /* workgroups of the dx launch */
+    int dw_band;        /* dy rows per thread of the partials launch */
+    int segments;       /* workgroups per plane of the partials launch: nine doubles of workspace each */
+    int dw_grid_x;      /* workgroups of the partials launch: N * C * segments (capped at 2^22; the finish has C) */
+    int launches;       /* of a call that wants both gradients: 3 (dx alone 1, dweight alone 2) */
+    int block;          /* threads per workgroup */
+} rroi_depthwise_backward_plan_info;
+int rroi_depthwise3x3_backward_hip(int dtype, const void* dy, const void* x, const void* weight, void* dx, void* dweight,
+                                   int batch_size, int channels, int height, int width, int stride, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+/* host only; 0 for arguments the call would refuse */
+size_t rroi_depthwise3x3_backward_workspace_bytes(int batch_size, int channels, int height, int width, int stride);
+/* host only, no launch; 1, or 0 for arguments the call would refuse */
+int rroi_depthwise3x3_backward_plan(int dtype, int batch_size, int channels, int height, int width, int stride,
+                                    rroi_depthwise_backward_plan_info* plan);
+
+/* ------------------------------------------------------------------------- *
  * 6. The network's InstanceNorm2d with the activation that follows it, replacing the stock
  *    `nn.InstanceNorm2d(c, eps, affine)` of tools/models.py (MIOpen's spatial batch norm in fp32, two ATen kernels in
  *    16 bits) and, optionally, the LeakyReLU / ReLU launch behind it.  Forward only, instance statistics only (never
