@@ -40,7 +40,8 @@
 // rroi_detection_loss_kernels.h (+ rroi_detection_loss_host.h: the detection loss and its gradient),
 // rroi_instancenorm_backward_kernels.h (+ rroi_instancenorm_backward_host.h: the InstanceNorm's training forward and its
 // backward), rroi_depthwise_backward_kernels.h (+ rroi_depthwise_backward_host.h: the depthwise 3x3
-// convolution's input and weight gradients).
+// convolution's input and weight gradients), rroi_merge_backward_kernels.h (+ rroi_merge_backward_host.h: the
+// gated merge's backward, the stand-alone resize and its backward).
 // Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
 // launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
@@ -84,6 +85,7 @@ namespace {
 #include "rroi_detection_loss_kernels.h"
 #include "rroi_instancenorm_backward_kernels.h"
 #include "rroi_depthwise_backward_kernels.h"
+#include "rroi_merge_backward_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
@@ -102,6 +104,7 @@ namespace {
 #include "rroi_detection_loss_host.h"
 #include "rroi_instancenorm_backward_host.h"
 #include "rroi_depthwise_backward_host.h"
+#include "rroi_merge_backward_host.h"
 
 }  // namespace
 
@@ -889,6 +892,98 @@ int rroi_merge_forward_forced_hip(int dtype, const void* a, int a_h, int a_w, co
     return merge_impl(P, dtype, a, gate, f, y, channels, width, stream);
 }
 #endif
+
+// ------------------------------------------------------------------------------------
+// The stand-alone resize, its backward and the merge's backward (header section 8b): one launch each, two or
+// three and a workspace where dgate is wanted.
+// ------------------------------------------------------------------------------------
+int rroi_resize_footprint(int in, int out, int i, int* lo, int* hi)
+{
+    if (in < 1 || out < 1 || i < 0 || i >= in || !lo || !hi) return 0;
+    rs_footprint(merge_scale(in, out), in, out, i, lo, hi);
+    return 1;
+}
+
+int rroi_resize_forward_hip(int dtype, const void* x, void* y, int batch_size, int channels, int in_height, int in_width,
+                            int height, int width, void* stream_)
+{
+    const MergePlan P = plan_merge(dtype, batch_size, channels, height, width, in_height, in_width, 1, 1, 0, num_cus());
+    if (!P.status || !x || !y) return 0;
+    const size_t esize = dtype == RROI_DTYPE_FP32 ? 4 : 2, planes = (size_t)batch_size * channels;
+    if (bytes_overlap(y, planes * height * width * esize, x, planes * in_height * in_width * esize)) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_resize(P, static_cast<const T*>(x), static_cast<T*>(y), (unsigned)channels, (unsigned)width, stream);
+    });
+}
+
+int rroi_resize_backward_plan(int dtype, int batch_size, int channels, int in_height, int in_width, int height, int width,
+                              rroi_resize_backward_plan_info* plan)
+{
+    const ResizeBwdPlan P = plan_resize_backward(dtype, batch_size, channels, in_height, in_width, height, width, num_cus());
+    if (!P.status || !plan) return 0;
+    *plan = rroi_resize_backward_plan_info{1, P.K, (int)P.tiles, (int)P.grid, kMgThreads, (int)P.cb, P.ident ? 1 : 0,
+                                           P.max_rows, P.max_cols, P.sy, P.sx};
+    return 1;
+}
+
+int rroi_resize_backward_hip(int dtype, const void* dy, void* dx, int batch_size, int channels, int in_height, int in_width,
+                             int height, int width, void* stream_)
+{
+    const ResizeBwdPlan P = plan_resize_backward(dtype, batch_size, channels, in_height, in_width, height, width, num_cus());
+    if (!P.status || !dy || !dx) return 0;
+    const size_t esize = dtype == RROI_DTYPE_FP32 ? 4 : 2, planes = (size_t)batch_size * channels;
+    if (bytes_overlap(dx, planes * in_height * in_width * esize, dy, planes * height * width * esize)) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_resize_backward(P, static_cast<const T*>(dy), static_cast<T*>(dx), (unsigned)channels, in_height, in_width,
+                                      height, width, stream);
+    });
+}
+
+size_t rroi_merge_backward_workspace_bytes(int dtype, int batch_size, int channels, int height, int width, int g_h, int g_w)
+{
+    return plan_merge_backward(dtype, batch_size, channels, height, width, g_h, g_w, 1).ws_bytes;
+}
+
+int rroi_merge_backward_plan(int dtype, int batch_size, int channels, int height, int width, int g_h, int g_w, int gated,
+                             rroi_merge_backward_plan_info* plan)
+{
+    const MergeBwdPlan P = plan_merge_backward(dtype, batch_size, channels, height, width, g_h, g_w, gated);
+    if (!P.status || !plan) return 0;
+    // launches: of a call that wants dgate (df alone is one; the blocks' sum is a launch of its own where there are several)
+    *plan = rroi_merge_backward_plan_info{P.V, P.K, (int)P.tiles, (int)P.grid, kMgThreads, (int)P.cb, (int)P.gtiles,
+                                          (int)P.ggrid, P.resize_g ? 1 : 0, P.gated ? (P.K > 1 ? 3 : 2) : 1, (long long)P.ws_bytes,
+                                          P.G.sy, P.G.sx};
+    return 1;
+}
+
+int rroi_merge_backward_hip(int dtype, const void* dy, const void* f, const void* gate, void* df, void* dgate, int batch_size,
+                            int channels, int height, int width, int g_h, int g_w, void* workspace, size_t workspace_bytes,
+                            void* stream_)
+{
+    const MergeBwdPlan P = plan_merge_backward(dtype, batch_size, channels, height, width, g_h, g_w, gate ? 1 : 0);
+    if (!P.status) return 0;
+    if (!dy || !f || (!df && !dgate) || (dgate && !gate)) return 0;
+    const size_t esize = dtype == RROI_DTYPE_FP32 ? 4 : 2;
+    const size_t map_bytes = (size_t)batch_size * channels * P.hw * esize, gate_bytes = (size_t)batch_size * P.ghw * esize;
+    for (const void* in : {dy, f}) {
+        if (bytes_overlap(df, map_bytes, in, map_bytes) || bytes_overlap(dgate, gate_bytes, in, map_bytes)) return 0;
+    }
+    if (bytes_overlap(df, map_bytes, gate, gate_bytes) || bytes_overlap(dgate, gate_bytes, gate, gate_bytes) ||
+        bytes_overlap(df, map_bytes, dgate, gate_bytes))
+        return 0;
+    if (dgate && (!workspace_ok(workspace) || workspace_bytes < P.ws_bytes)) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_merge_backward(P, static_cast<const T*>(dy), static_cast<const T*>(f), static_cast<const T*>(gate),
+                                     static_cast<T*>(df), static_cast<T*>(dgate), (unsigned)channels, height, width, workspace,
+                                     stream);
+    });
+}
 
 // ------------------------------------------------------------------------------------
 // Dense 3x3 convolution on the matrix cores, bfloat16 / float16 (header section 9): one launch, no workspace.

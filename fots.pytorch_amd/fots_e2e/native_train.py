@@ -1,5 +1,5 @@
 """fots_e2e.native_train -- the operators of FOTSNet that stay on the package's own kernels when a gradient is needed:
-InstanceNorm2d (below) and the depthwise 3x3 convolution (at the end of the file).
+InstanceNorm2d (below), the depthwise 3x3 convolution and the feature merge (at the end of the file).
 
 Every switch of `fots_e2e.native` is inference only: a call that needs a gradient takes the stock path.  The most frequent
 operator of the network, InstanceNorm2d (49 calls per pass, instance statistics in training as in the reference), has a
@@ -20,6 +20,12 @@ already falls back to the block's modules one by one, so all 22 are reached; the
 Channels-last inputs and autocast keep the stock path; a double backward needs it too (the function is once
 differentiable, and whether a graph of the backward will be wanted is not known when the forward runs): switch back with
 `enable=False` for one.
+
+The stretch between them, the feature merge -- six bilinear resizes per pass, whose stock backward scatters with atomics
+and raises under `torch.use_deterministic_algorithms(True)` -- has native gradients too:
+`use_trainable_merge(net)` -- called after `native.use_native_merge` -- switches the network's class to a subclass whose
+`_merge`, in training mode, runs the three merges and the two stand-alone resizes through `rroi_align.merge`'s autograd
+functions where a gradient is needed and `trainable_merge_ok` holds.
 
 It lives in a module of its own for the reason `native_remainder` does: the `_*_slower` hooks of `fots_e2e.native` are a
 closed list that the network tests read."""
@@ -158,3 +164,124 @@ def use_trainable_depthwise(net: nn.Module, enable: bool = True) -> int:
             m.__class__ = dst
             n += 1
     return n
+
+
+# --------------------------------------------------------------------------- the feature merge, DESIGN 5.26
+_MERGE = []
+_MAX_FOOTPRINT = 4096     # kRsMaxFootprint of csrc/rroi_merge_backward_kernels.h
+
+
+def _merge_fn():
+    """`rroi_align.merge`, loaded on first use, as `_norm`."""
+    if not _MERGE:
+        from rroi_align import merge
+        _MERGE.append(merge)
+    return _MERGE[0]
+
+
+def _footprint_bound(n_in: int, n_out: int) -> int:
+    """rs_max_footprint of csrc/rroi_merge_backward_host.h, mirrored: an upper bound of the output rows that meet in one
+    source row; the library refuses a backward above `_MAX_FOOTPRINT`."""
+    if n_out == 1:
+        return 1
+    if n_in == 1:
+        return n_out
+    return min(n_out, int(2.0 / ((n_in - 1) / (n_out - 1))) + 2)
+
+
+def _gather_ok(src, like) -> bool:
+    return all(_footprint_bound(i, o) <= _MAX_FOOTPRINT for i, o in zip(src.shape[2:], like.shape[2:]))
+
+
+def trainable_merge_ok(a, f, gate=None, resize_only: bool = False) -> bool:
+    """True where `up(a) + f * up(gate)` (resize_only: `up(a)` alone, to f's size) may run the native forward and backward
+    when a gradient is needed: `native.merge_ok`'s conditions other than its gradient clause (asked with gradients off, so
+    that there is one copy of them), a resize the backward's gather accepts (at most 4096 output rows or columns meeting in
+    one source element), and not a shape class whose forward + backward measured slower (`_merge_backward_slower`; not
+    asked under `torch.use_deterministic_algorithms(True)`, where the stock backward raises and speed is no reason to
+    take it).  Pure, no GPU needed to ask."""
+    with torch.no_grad():
+        return (_nat.merge_ok(a, f, gate) and _gather_ok(a, f) and (gate is None or _gather_ok(gate, f))
+                and (torch.are_deterministic_algorithms_enabled() or not _merge_backward_slower(a, f, gate, resize_only)))
+
+
+def _merge_backward_slower(a, f, gate, resize_only) -> bool:
+    """The shape classes in which native forward + backward did not meet the bar of DESIGN 5.10 against autograd of the
+    stock expression in BOTH runs (profiles/native_merge_backward.md, microseconds per forward + backward, native median /
+    stock minimum, two runs of 30 rows: the network's three merges and two resizes at 704 x 1280, one and eight images,
+    three dtypes).  Both are gated merges at one image, where both legs stand at the floor of issuing a forward + backward
+    from Python and the native one, with its four or five launches, does not get below it:
+      `a` of f's size, 1.8e6 to 9.0e6 elements in f, any dtype -- the one measured row is the second merge at one image,
+        256 x 88 x 160 = 3.6e6: float32 84.5 / 79.6 and 85.2 / 77.1, bfloat16 79.8 / 78.6 and 76.6 / 70.6, float16
+        77.8 / 73.5 and 81.2 / 78.3.  Its neighbours win: the third merge at one image (1.44e7 elements: 125.2 / 151.0,
+        77.7 / 92.3, 77.7 / 89.4) and itself at eight images (2.9e7: 194.9 / 287.6, 106.3 / 184.9, 107.1 / 177.3).
+      float32, `a` resized, 4.5e5 to 4.05e6 elements in f -- the first merge at one image, 256 x 44 x 80 = 9.0e5:
+        172.2 / 127.3 and 132.2 / 127.9, rounds from 87 to 304; float16 wins twice (88.0 / 97.2, 87.1 / 96.9), bfloat16
+        misses once and is no class (179.1 / 104.6, then 88.0 / 104.2), and at eight images (7.2e6) every dtype wins 7-9 x.
+    The upper lines are halfway to the next measured row and the lower ones at half the measured size, as
+    `_inorm_backward_slower` draws them; nothing smaller was measured and it stays native.  No stand-alone resize misses.
+    Under `torch.use_deterministic_algorithms(True)` the predicate does not ask this hook: the stock backward raises there."""
+    if resize_only or gate is None:
+        return False
+    n = f.numel()
+    if a.shape[2:] == f.shape[2:]:
+        return 1_800_000 <= n < 9_000_000
+    return f.dtype == torch.float32 and 450_000 <= n < 4_050_000
+
+
+class _TrainableMerge:
+    """Mixin in front of a `*Merge*FOTSNet`: in training mode, where a gradient is needed, `_merge` runs the three merges
+    through `rroi_align.merge.gated_merge` -- the gate at its source's size from `torch.sigmoid(self.conv_attenton(t))`
+    under stock autograd -- and the two resizes in front of `upconv1` / `upconv2` through `bilinear_resize`, each where
+    `trainable_merge_ok` holds and as `FOTSNet._merge`'s expression where it does not.  Everywhere else it is its parent."""
+
+    def _train_resize(self, t, like):
+        if trainable_merge_ok(t, like, None, True):
+            return _merge_fn()._BilinearResize.apply(t, like.size(2), like.size(3))
+        return self._up(t, like)
+
+    def _train_merge_one(self, a, f, t):
+        g = torch.sigmoid(self.conv_attenton(t)) if self.attention else None
+        if trainable_merge_ok(a, f, g):
+            return _merge_fn()._GatedMerge.apply(a, f, g)
+        A = a if a.shape[2:] == f.shape[2:] else self._up(a, f)
+        return A + f if g is None else A + f * self._up(g, f)
+
+    def _merge(self, f1, f2, f3, f4):
+        if not (self.training and torch.is_grad_enabled()
+                and (any(isinstance(t, torch.Tensor) and t.requires_grad for t in (f1, f2, f3, f4))
+                     or (self.attention and any(p.requires_grad for p in self.conv_attenton.parameters()))
+                     or any(p.requires_grad for m in (self.upconv1, self.upconv2) for p in m.parameters()))):
+            return super()._merge(f1, f2, f3, f4)
+        t = self._train_merge_one(f4, f3, f4)
+        m2 = self._train_merge_one(self.upconv1(self._train_resize(t, f2)), f2, t)
+        m1 = self._train_merge_one(self.upconv2(self._train_resize(m2, f1)), f1, m2)
+        return m1, m2
+
+
+class TrainableMergeFOTSNet(_TrainableMerge, _nat.NativeMergeFOTSNet):
+    """A `NativeMergeFOTSNet` (same modules, same `state_dict` keys) whose feature merge stays native in training."""
+
+
+class TrainableHeadsMergeFOTSNet(_TrainableMerge, _nat.NativeHeadsMergeFOTSNet):
+    """A `NativeHeadsMergeFOTSNet` whose feature merge stays native in training."""
+
+
+class TrainableMergeRecogniserFOTSNet(_TrainableMerge, _nat.NativeMergeRecogniserFOTSNet):
+    """A `NativeMergeRecogniserFOTSNet` whose feature merge stays native in training."""
+
+
+class TrainableHeadsMergeRecogniserFOTSNet(_TrainableMerge, _nat.NativeHeadsMergeRecogniserFOTSNet):
+    """A `NativeHeadsMergeRecogniserFOTSNet` whose feature merge stays native in training."""
+
+
+def use_trainable_merge(net: nn.Module, enable: bool = True) -> bool:
+    """Switch a network whose type is exactly one of the four `*Merge*FOTSNet` classes of `fots_e2e.native` to its trainable
+    subclass (enable=False: back), so call it after `native.use_native_merge` -- and after `use_native_heads` /
+    `use_native_recogniser`, which look for the exact types they know -- and undo it before undoing those.  Only the class
+    of the network changes: no parameter is copied, no key of the state_dict moves.  A network of any other type is left
+    alone.  Returns whether the class was switched."""
+    return _nat._switch_class(net, ((_nat.NativeMergeFOTSNet, TrainableMergeFOTSNet),
+                                    (_nat.NativeHeadsMergeFOTSNet, TrainableHeadsMergeFOTSNet),
+                                    (_nat.NativeMergeRecogniserFOTSNet, TrainableMergeRecogniserFOTSNet),
+                                    (_nat.NativeHeadsMergeRecogniserFOTSNet, TrainableHeadsMergeRecogniserFOTSNet)), enable)

@@ -45,7 +45,10 @@ from .instancenorm import (INORM_PLANE, INORM_SPLIT, InstanceNormPlan, _InormPla
                            instance_norm_train, instance_norm_workspace_bytes, run_instance_norm_backward,
                            run_instance_norm_train)
 from .heads import HeadsPlan, _gate_run, _heads_run, _HeadsPlan, _require_pointwise, gate, heads, heads_plan  # noqa: F401
-from .merge import MergePlan, _gated_merge_run, _MergePlan, gated_merge, merge_plan  # noqa: F401
+from .merge import (MergeBackwardPlan, MergePlan, ResizeBackwardPlan, _gated_merge_run, _MergeBwdPlan, _MergePlan,  # noqa: F401
+                    _ResizeBwdPlan, gated_merge, gated_merge_backward, merge_backward_plan, merge_backward_workspace_bytes,
+                    merge_plan, resize_backward_plan, resize_bilinear, resize_bilinear_backward, resize_footprint,
+                    run_gated_merge_backward, run_resize_bilinear, run_resize_bilinear_backward)
 from .conv3x3 import Conv3x3Plan, _conv3x3_run, _ConvPlan, conv3x3, conv3x3_plan  # noqa: F401
 from .conv1x1 import Conv1x1Plan, _conv1x1_run, _Conv1x1Plan, conv1x1, conv1x1_plan  # noqa: F401
 from .recogniser import (OCR_HEAD_MAX_CLASSES, OcrHeadPlan, _act_maxpool2x1_run, _ocr_head_run, _OcrHeadPlan,  # noqa: F401
@@ -80,4 +83,6 @@ EXPORTS = (
     "rroi_instancenorm_forward_train_hip", "rroi_instancenorm_backward_hip", "rroi_instancenorm_backward_workspace_bytes",
     "rroi_instancenorm_backward_plan",   # bound in instancenorm.py
     "rroi_depthwise3x3_backward_hip", "rroi_depthwise3x3_backward_workspace_bytes", "rroi_depthwise3x3_backward_plan",
+    "rroi_resize_forward_hip", "rroi_resize_backward_hip", "rroi_resize_footprint", "rroi_resize_backward_plan",
+    "rroi_merge_backward_hip", "rroi_merge_backward_workspace_bytes", "rroi_merge_backward_plan",   # bound in merge.py
 )

@@ -176,3 +176,30 @@ def _require_depthwise_device(x, weight, name: str) -> None:
         raise ValueError(f"{name} and weight must be on the same device")
     if x.size(1) < 1 or x.size(2) < 1 or x.size(3) < 1:
         raise ValueError(f"{name} must have at least one channel, row and column, got {tuple(x.shape)}")
+
+
+def _require_map(t, name: str, like=None, like_name: str = "") -> None:
+    """What the resize and merge-backward calls ask of every tensor: a 4-D (N,C,H,W) tensor with at least one channel, row
+    and column, on the GPU, float32 / bfloat16 / float16 -- and, given `like`, of its dtype and device."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.dim() != 4:
+        raise ValueError(f"{name} must be 4-D (N,C,H,W), got {tuple(t.shape)}")
+    if like is not None and t.dtype != like.dtype:
+        raise ValueError(f"{name} and {like_name} must have one dtype, got {t.dtype} and {like.dtype}")
+    _require_cuda_f32(t, name, _IO_DTYPES)
+    if like is not None and t.device != like.device:
+        raise ValueError(f"{name} and {like_name} must be on the same device")
+    if min(t.shape[1:]) < 1:
+        raise ValueError(f"{name} must have at least one channel, row and column, got {tuple(t.shape)}")
+
+
+def _size2(size, name: str):
+    """(h, w) of a `size` argument: two positive integers."""
+    try:
+        h, w = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be two integers (h, w), got {size!r}") from None
+    if h < 1 or w < 1:
+        raise ValueError(f"{name} must be positive, got {size!r}")
+    return h, w

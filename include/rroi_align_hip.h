@@ -809,6 +809,101 @@ int rroi_merge_plan(int dtype, int batch_size, int channels, int height, int wid
                     int gated, rroi_merge_plan_info* plan);
 
 /* ------------------------------------------------------------------------- *
+ * 8b. The backward of section 8's merge, the resize R of section 8 on its own, and its backward, all
+ *    deterministic and free of atomics.  Opt-in from Python (rroi_align.merge.gated_merge / bilinear_resize,
+ *    fots_e2e.native_train.use_trainable_merge).  R is section 8's resize with its scales, indices and weights; the
+ *    forward is y = R_a a + f * (R_g gate).  All tensors contiguous NCHW of one element type `dtype`; any element-aligned
+ *    address works.
+ *
+ *    rroi_resize_forward_hip:   x (N, C, in_height, in_width) -> y (N, C, height, width) = R x: section 8's `value`,
+ *      rounded as its `out` is -- (T)(float)z -- so bit for bit what section 8 adds as A.  A source of y's size is copied
+ *      as it is.  Every element of y is written and nothing else is.  One launch, no workspace.
+ *
+ *    rroi_resize_backward_hip:  dy (N, C, height, width) -> dx (N, C, in_height, in_width) = R^T dy, as a gather, the exact
+ *      transpose of the forward's own index decisions: output row Y gives weight 1 - l1 to source row i0(Y) and l1 to
+ *      i0(Y) + step(Y), step = min(i0 + 1, in - 1) - i0; columns likewise.  The rows that reach source row i are the
+ *      contiguous range rroi_resize_footprint reports.  Per element, in double, every operation rounded separately:
+ *          acc = +0.0;  for Y of the range, ascending:
+ *              row = +0.0;  for X of the column range, ascending:  row = row + wx * (double)dy[n, c, Y, X]
+ *              acc = acc + wy * row
+ *      where step == 0 both weights meet in one element and are two terms, the first tap's and then the second's.  No tap
+ *      of the range is skipped: a zero weight against an infinity is NaN, as in the forward.  dx = one rounding of acc from
+ *      double to `dtype` (the 16-bit types through a float rounded to odd, as in sections 15, 6c and 5b).  EVERY element of
+ *      dx is written, +0.0 where no output pixel reaches it, and nothing else is.  Sizes that agree: dx is dy's values.
+ *      One launch, no workspace.
+ *
+ *    rroi_merge_backward_hip:   dy, f (N, C, H, W), gate (N, 1, g_h, g_w) or NULL -> df (N, C, H, W) and / or
+ *      dgate (N, 1, g_h, g_w); either may be NULL, not both; dgate needs the gate.  (da needs no call: it is dy where a has
+ *      f's size and rroi_resize_backward_hip of dy otherwise; without a gate df is dy.)
+ *        df = (T)(float)((double)dy * G), G recomputed per pixel exactly as section 8 computes it (1 without a gate):
+ *          bit for bit a float64 restatement.
+ *        dgate = R_g^T S,  S[n, Y, X] = sum over c of (double)dy * (double)f (each product exact in double): first per
+ *          block of `channel_block` consecutive channels, c ascending, into the workspace ([n][block][pixel], doubles),
+ *          then the blocks ascending (a launch of its own where there is more than one, in place into block 0), then the
+ *          gather of rroi_resize_backward_hip on those doubles (the identity where the gate has f's size), one rounding to
+ *          `dtype`.  The blocks are a function of (N, C, H, W) alone -- never of the device -- so the bits are the same on
+ *          every device and run.  Two or three launches (df alone: one).
+ *      The workspace: rroi_merge_backward_workspace_bytes(...) bytes at a 256-byte-aligned address where dgate is wanted;
+ *      its contents before and after the call mean nothing.  Where dgate is NULL it is not needed: NULL / 0 is accepted
+ *      and a buffer that is handed over is left alone.
+ *
+ *    No chain of additions exceeds 8192 terms: channel blocks hold at most 2048 channels, and the host refuses more than
+ *    4096 blocks and a resize in which more than 4096 output rows (columns) would meet in one source row (column) --
+ *    judged by an upper bound: out where in == 1, else min(out, (long long)(2 / s) + 2); a 2x resize has 5.
+ *
+ *    Returns 1 / 0 / -hipError.  0, before any launch: an unknown dtype, a dimension below 1, a tensor of 2^31 elements or
+ *    more, the chain limits above, a NULL input or output pointer (dy, f always; the gate where dgate is wanted; df and
+ *    dgate both NULL), an output overlapping an input or the other output, and -- where dgate is wanted -- a NULL workspace,
+ *    one that is not a multiple of 256, or workspace_bytes below the size query's answer.  Every call only enqueues on
+ *    `stream`, allocates nothing and can be captured into a HIP graph.
+ *    Arrived after 0.10.0 under the same version string: detect it by symbol.
+ * ------------------------------------------------------------------------- */
+typedef struct rroi_resize_backward_plan_info {
+    int vector_elems;    /* dx elements per lane: 1 */
+    int channel_groups;  /* K: workgroups per tile, each on its own block of channels (the bits do not depend on it) */
+    int tiles;           /* tiles of 256 dx pixels per image */
+    int grid_x;          /* workgroups: N * K * tiles */
+    int block;           /* threads per workgroup: 256 */
+    int channel_block;   /* ceil(C / K) */
+    int identity;        /* 1: the sizes agree, dx is dy's values */
+    int max_rows;        /* the upper bound of the output rows that meet in one source row (refused above 4096) */
+    int max_cols;        /* likewise for columns */
+    double scale_y, scale_x;
+} rroi_resize_backward_plan_info;
+typedef struct rroi_merge_backward_plan_info {
+    int vector_elems;    /* V: consecutive pixels per lane of the first launch: 4 */
+    int channel_groups;  /* channel blocks, a function of the shape alone */
+    int tiles;           /* tiles of 256 * V pixels per image */
+    int grid_x;          /* workgroups of the first launch: N * channel_groups * tiles */
+    int block;           /* threads per workgroup: 256 */
+    int channel_block;   /* channels per block: at most 2048, at least 32 in the last one where there are several */
+    int gate_tiles;      /* tiles of 256 gate pixels per image of the dgate launch (0 without a gate) */
+    int gate_grid_x;     /* its workgroups: N * gate_tiles */
+    int resize_gate;     /* 1: the gate is interpolated; 0: it has f's size (or there is none) */
+    int launches;        /* of a call that wants dgate: 2, 3 with more than one channel block (df alone, or no gate: 1) */
+    long long workspace_bytes;   /* what dgate needs: N * channel_groups * H * W doubles, rounded up to 256 (0 without a gate) */
+    double gate_scale_y, gate_scale_x;
+} rroi_merge_backward_plan_info;
+int rroi_resize_forward_hip(int dtype, const void* x, void* y, int batch_size, int channels, int in_height, int in_width,
+                            int height, int width, void* stream);
+int rroi_resize_backward_hip(int dtype, const void* dy, void* dx, int batch_size, int channels, int in_height, int in_width,
+                             int height, int width, void* stream);
+/* host only: the output indices [*lo, *hi) of an axis resized from `in` to `out` whose taps reach source index i (empty:
+ * *lo == *hi); 1, or 0 for in or out below 1, i outside [0, in) or a NULL pointer */
+int rroi_resize_footprint(int in, int out, int i, int* lo, int* hi);
+/* host only, no launch; 1, or 0 for arguments the call would refuse */
+int rroi_resize_backward_plan(int dtype, int batch_size, int channels, int in_height, int in_width, int height, int width,
+                              rroi_resize_backward_plan_info* plan);
+int rroi_merge_backward_hip(int dtype, const void* dy, const void* f, const void* gate, void* df, void* dgate, int batch_size,
+                            int channels, int height, int width, int g_h, int g_w, void* workspace, size_t workspace_bytes,
+                            void* stream);
+/* host only; what dgate needs for a gate of (g_h, g_w); 0 for arguments the call would refuse */
+size_t rroi_merge_backward_workspace_bytes(int dtype, int batch_size, int channels, int height, int width, int g_h, int g_w);
+/* host only, no launch; 1, or 0 for arguments the call would refuse; gated: 1 (g_h, g_w are the gate's size) or 0 */
+int rroi_merge_backward_plan(int dtype, int batch_size, int channels, int height, int width, int g_h, int g_w, int gated,
+                             rroi_merge_backward_plan_info* plan);
+
+/* ------------------------------------------------------------------------- *
  * 9. The network's dense 3x3 convolution on the matrix cores, bfloat16 / float16:
  *    y = act(conv2d(x, w, stride, padding = 1)) in ONE launch.  Forward only; opt-in from Python
  *    (fots_e2e.native.use_native_conv3x3).
@@ -1236,7 +1331,7 @@ int rroi_align_get_trig_recipe_hip(void);
  * the same version string: a caller detects them by symbol.  So did the bucketed calls of section 2b, the depthwise
  * convolution of section 5, the InstanceNorm of section 6, its fused epilogues of section 6b, its training calls of section 6c, the heads and gate of section 7, the gated merge
  * of section 8, the dense 3x3 convolution of section 9, the recogniser's head and activation + pool of section 10 and the 1x1
- * convolution of section 11, and the calls of sections 12 to 16. */
+ * convolution of section 11, the calls of sections 12 to 16, and the backward calls of sections 5b and 8b. */
 const char* rroi_align_hip_version(void);
 
 #ifdef __cplusplus
