@@ -59,37 +59,67 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _switching as _sw
 from .model import FOTSNet, _MirrorNorm, _PlainBlock, _SeparableBlock
 
 _DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+_CONV_DTYPES = (torch.bfloat16, torch.float16)   # the matrix-core convolutions': float32 keeps the stock kernels
+_STRIDES = ((1, 1), (2, 2))
+
+_ext = _sw.lazy_module("rroi_align._ext.rroi_align")   # the ctypes binding, loaded on first use
 
 
+# --------------------------------------------------------------------------- the clauses every predicate shares
+def _tensor_ok(x, dtypes=_DTYPES) -> bool:
+    """A contiguous 4-D CUDA tensor of one of `dtypes` with 1 to 2^31 - 1 elements.  Every predicate asks this first: a CPU
+    tensor is declined before a parameter is read or the library loaded."""
+    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype in dtypes and x.is_contiguous()
+            and 0 < x.numel() < (1 << 31))
+
+
+def _inference(*tensors) -> bool:
+    """No autocast (it changes the stock module's output dtype: left to it), and no gradient needed by any of `tensors`
+    (None: absent).  Every predicate asks this last."""
+    return not torch.is_autocast_enabled() and not (torch.is_grad_enabled()
+                                                    and any(t is not None and t.requires_grad for t in tensors))
+
+
+def _conv_static_ok(m, kernel, padding, strides=_STRIDES) -> bool:
+    """A convolution of exactly this kernel and padding, a stride of `strides`, no dilation, no bias, zero padding."""
+    return (m.kernel_size == kernel and m.padding == padding and m.dilation == (1, 1) and m.stride in strides
+            and m._parameters["bias"] is None and m.padding_mode == "zeros")
+
+
+def _conv_operands_ok(m, x) -> bool:
+    """x has the weight's dtype, device and input channels."""
+    w = m._parameters["weight"]
+    return x.dtype == w.dtype and w.device == x.device and x.size(1) == m.in_channels
+
+
+def _conv_out_numel(m, x) -> int:
+    """The elements of `m(x)` for a convolution whose padding keeps the size at stride 1."""
+    s = m.stride[0]
+    return x.size(0) * m.out_channels * ((x.size(2) - 1) // s + 1) * ((x.size(3) - 1) // s + 1)
+
+
+def _matrix_conv_ok(m, x, static_ok) -> bool:
+    """What the matrix-core convolutions ask of their operands: a 16-bit x, a module `static_ok` accepts, a contiguous
+    weight of x's dtype on x's device, fewer than 2^31 elements out."""
+    return (_tensor_ok(x, _CONV_DTYPES) and static_ok(m) and _conv_operands_ok(m, x)
+            and m._parameters["weight"].is_contiguous() and _conv_out_numel(m, x) < (1 << 31))
+
+
+# --------------------------------------------------------------------------- depthwise 3x3 convolution, DESIGN 5.10
 def _static_ok(m) -> bool:
     """What of `native_ok` depends on the module alone: a depthwise 3x3, padding 1, stride 1 or 2, no bias."""
-    return (m.kernel_size == (3, 3) and m.padding == (1, 1) and m.dilation == (1, 1) and m.stride in ((1, 1), (2, 2))
-            and m.groups == m.in_channels == m.out_channels and m._parameters["bias"] is None and m.padding_mode == "zeros")
+    return _conv_static_ok(m, (3, 3), (1, 1)) and m.groups == m.in_channels == m.out_channels
 
 
 def native_ok(m, x) -> bool:
-    """True where `m(x)` may run the native kernel: pure, no GPU needed to ask.  (Cheapest tests first, parameters read
-    from `_parameters`: the network asks 22 times per pass.)"""
-    w = m._parameters["weight"]
-    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype == w.dtype and x.dtype in _DTYPES
-            and x.is_contiguous() and _static_ok(m) and x.size(1) == m.in_channels and w.device == x.device
-            and 0 < x.numel() < (1 << 31)
-            and not torch.is_autocast_enabled()   # (autocast changes the stock module's output dtype: left to it)
-            and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)))
-
-
-_EXT = []
-
-
-def _ext():
-    """The ctypes binding, loaded on first use: asking `native_ok` needs neither the library nor a GPU."""
-    if not _EXT:
-        from rroi_align._ext import rroi_align as ext
-        _EXT.append(ext)
-    return _EXT[0]
+    """True where `m(x)` may run the native kernel: pure, no GPU needed to ask.  (Parameters are read from `_parameters`:
+    the network asks 22 times per pass.)"""
+    return (_tensor_ok(x) and _static_ok(m) and _conv_operands_ok(m, x)
+            and _inference(x, m._parameters["weight"]))
 
 
 class DepthwiseConv3x3(nn.Conv2d):
@@ -106,13 +136,7 @@ def use_native_depthwise(net: nn.Module, enable: bool = True) -> int:
     """Switch every qualifying `nn.Conv2d` of `net` to `DepthwiseConv3x3` (enable=False: back).  Only the class of the
     module changes: no parameter is copied, no key of the state_dict moves.  Returns the number of modules switched
     (22 for `FOTSNet()`)."""
-    src, dst = (nn.Conv2d, DepthwiseConv3x3) if enable else (DepthwiseConv3x3, nn.Conv2d)
-    n = 0
-    for m in net.modules():
-        if type(m) is src and (not enable or _static_ok(m)):
-            m.__class__ = dst
-            n += 1
-    return n
+    return _sw.swap_classes(net, ((nn.Conv2d, DepthwiseConv3x3),), enable, _static_ok)[0]
 
 
 # --------------------------------------------------------------------------- InstanceNorm2d (+ activation), DESIGN 5.11
@@ -125,14 +149,15 @@ def instancenorm_ok(m, x) -> bool:
 
 def _inorm_ok(m, x, widen) -> bool:
     """`instancenorm_ok` for a norm of `widen` times x's channels (2: the stem's mirror, which widens x on the way in)."""
+    if not _tensor_ok(x):
+        return False
     w = m._parameters.get("weight")
-    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype in _DTYPES and x.is_contiguous()
-            and not m.track_running_stats and widen * x.size(1) == m.num_features and 0 < widen * x.numel() < (1 << 31)
+    b = None if w is None else m._parameters.get("bias")
+    return (not m.track_running_stats and widen * x.size(1) == m.num_features
+            and (widen == 1 or widen * x.numel() < (1 << 31))
             and x.size(2) * x.size(3) > 1 and not _inorm_slower(x)
-            and (w is None or (w.dtype == x.dtype and w.device == x.device and m._parameters.get("bias") is not None))
-            and not torch.is_autocast_enabled()
-            and not (torch.is_grad_enabled() and (x.requires_grad or (w is not None and (w.requires_grad
-                                                                                         or m._parameters["bias"].requires_grad)))))
+            and (w is None or (w.dtype == x.dtype and w.device == x.device and b is not None))
+            and _inference(x, w, b))
 
 
 def _inorm_slower(x) -> bool:
@@ -182,43 +207,13 @@ def use_native_instancenorm(net: nn.Module, enable: bool = True, fuse_activation
     `fuse_activation` -- let every switched norm that an `nn.Sequential` follows directly with an `nn.LeakyReLU` /
     `nn.ReLU` take over that activation's slope, the activation becoming a pass-through (20 pairs for `FOTSNet()`).  A pair
     is fused only where both modules occur once in `net`: a module that is also called from somewhere else keeps its
-    meaning.  enable=False: every class back, every slope removed.  Only classes change: no parameter is copied, no key of
-    the state_dict moves.  Activations applied functionally (`F.leaky_relu` in a forward) stay what they are.
-    Returns (norms switched, activations switched)."""
-    norms = acts = 0
-    if not enable:
-        for m in net.modules():
-            if type(m) is NativeInstanceNorm2d:
-                m.__dict__.pop("fused_slope", None)
-                m.__class__ = nn.InstanceNorm2d
-                norms += 1
-            else:
-                for stock, absorbed in _ABSORBED.items():
-                    if type(m) is absorbed:
-                        m.__class__ = stock
-                        acts += 1
-        return norms, acts
-    for m in net.modules():
-        if type(m) is nn.InstanceNorm2d:
-            m.__class__ = NativeInstanceNorm2d
-            norms += 1
-    if fuse_activation:
-        uses = {}
-        for m in net.modules():
-            for child in m._modules.values():
-                if child is not None:
-                    uses[id(child)] = uses.get(id(child), 0) + 1
-        for seq in net.modules():
-            if not isinstance(seq, nn.Sequential):
-                continue
-            mods = list(seq._modules.values())
-            for norm, act in zip(mods, mods[1:]):
-                if (type(norm) is NativeInstanceNorm2d and norm.fused_slope is None and type(act) in _ABSORBED
-                        and uses[id(norm)] == 1 and uses[id(act)] == 1):
-                    norm.fused_slope = float(getattr(act, "negative_slope", 0.0))
-                    act.__class__ = _ABSORBED[type(act)]
-                    acts += 1
-    return norms, acts
+    meaning.  enable=False: every `NativeInstanceNorm2d` back, its slope removed and the activation behind it restored with
+    it.  A norm that `native_train.use_trainable_instancenorm` has switched further is not this switch's to restore, so it
+    keeps its slope and its pass-through activation, the call reports (0, 0) and the network computes what it did; undo
+    the trainable switch first, and the same call restores everything.  Only classes change: no parameter is copied, no
+    key of the state_dict moves.  Activations applied functionally (`F.leaky_relu` in a forward) stay what they are.
+    How the switches compose and undo: `fots_e2e._switching`.  Returns (norms switched, activations switched)."""
+    return _sw.swap_absorbing(net, nn.InstanceNorm2d, NativeInstanceNorm2d, _ABSORBED, enable, fuse_activation)
 
 
 # --------------------------------------------------------------------------- detection heads and attention gate, DESIGN 5.12
@@ -241,7 +236,8 @@ def _pointwise_conv_ok(m, outputs, t) -> bool:
 def heads_ok(net, t, gate: bool = False) -> bool:
     """True where `net._heads(t)` (gate=True: the convolution and sigmoid of `net._gate(t, like)`) may run the native
     kernel: pure, no GPU needed to ask.  No shape class is declined for speed: every measured one won
-    (profiles/native_heads.md)."""
+    (profiles/native_heads.md).
+    (The clauses of `_tensor_ok` and `_inference` written out: through the helpers this predicate measured slower.)"""
     return (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 4 and t.dtype in _DTYPES and t.is_contiguous()
             and 0 < t.numel() < (1 << 31)
             and not torch.is_autocast_enabled()
@@ -269,25 +265,12 @@ class NativeHeadsFOTSNet(FOTSNet):
         return super()._gate(t, like)
 
 
-def _switch_class(net, pairs, enable) -> bool:
-    """`net.__class__` from the first to the second class of the pair whose first (enable=False: second) is exactly its type."""
-    for stock, native in pairs:
-        src, dst = (stock, native) if enable else (native, stock)
-        if type(net) is src:
-            net.__class__ = dst
-            return True
-    return False
-
-
 def use_native_heads(net: nn.Module, enable: bool = True) -> bool:
     """Switch a network whose type is exactly `FOTSNet` to `NativeHeadsFOTSNet` (enable=False: back), and one that
-    `use_native_merge` has switched, `NativeMergeFOTSNet`, to `NativeHeadsMergeFOTSNet`; likewise the two types that
-    `use_native_recogniser` makes of those.  Only the class of the network changes: no parameter is copied, no key of the
-    state_dict moves; the module switches above, `use_native_merge` and `use_native_recogniser` compose with it in any
-    order.  A network of any other type is left alone.  Returns whether the class was switched."""
-    return _switch_class(net, ((FOTSNet, NativeHeadsFOTSNet), (NativeMergeFOTSNet, NativeHeadsMergeFOTSNet),
-                               (NativeRecogniserFOTSNet, NativeHeadsRecogniserFOTSNet),
-                               (NativeMergeRecogniserFOTSNet, NativeHeadsMergeRecogniserFOTSNet)), enable)
+    `use_native_merge` / `use_native_recogniser` have switched to the class that has the heads as well (`_NETS` below).
+    Only the class of the network changes: no parameter is copied, no key of the state_dict moves.  A network of any
+    other type is left alone.  Returns whether the class was switched."""
+    return _sw.toggle_feature(net, _NETS, NativeHeadsFOTSNet, enable)
 
 
 # --------------------------------------------------------------------------- the feature merge, DESIGN 5.14
@@ -297,14 +280,12 @@ def merge_ok(a, f, gate=None) -> bool:
     size and channels, a one-channel gate with f's batch size, each of fewer than 2^31 elements, no autocast, no
     gradient needed."""
     ts = (f, a) if gate is None else (f, a, gate)
-    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 4 and t.is_contiguous() and 0 < t.numel() < (1 << 31)
-               for t in ts):
+    if not _tensor_ok(f):
         return False
-    return (f.dtype in _DTYPES and all(t.dtype == f.dtype and t.device == f.device for t in ts[1:])
+    like_f = (f.dtype,)
+    return (all(_tensor_ok(t, like_f) and t.device == f.device for t in ts[1:])
             and a.shape[:2] == f.shape[:2] and (gate is None or (gate.size(0) == f.size(0) and gate.size(1) == 1))
-            and not _merge_slower(a, f, gate)
-            and not torch.is_autocast_enabled()
-            and not (torch.is_grad_enabled() and any(t.requires_grad for t in ts)))
+            and not _merge_slower(a, f, gate) and _inference(*ts))
 
 
 def _merge_slower(a, f, gate) -> bool:
@@ -355,14 +336,11 @@ class NativeHeadsMergeFOTSNet(_NativeMerge, NativeHeadsFOTSNet):
 
 
 def use_native_merge(net: nn.Module, enable: bool = True) -> bool:
-    """Switch a network whose type is exactly `FOTSNet` to `NativeMergeFOTSNet`, or exactly `NativeHeadsFOTSNet` to
-    `NativeHeadsMergeFOTSNet` (enable=False: back); likewise the two types that `use_native_recogniser` makes of those.
-    Only the class of the network changes: no parameter is copied, no key of the state_dict moves; it composes with
-    `use_native_heads`, `use_native_recogniser` and the module switches in any order.  A network of any other type is
-    left alone.  Returns whether the class was switched."""
-    return _switch_class(net, ((FOTSNet, NativeMergeFOTSNet), (NativeHeadsFOTSNet, NativeHeadsMergeFOTSNet),
-                               (NativeRecogniserFOTSNet, NativeMergeRecogniserFOTSNet),
-                               (NativeHeadsRecogniserFOTSNet, NativeHeadsMergeRecogniserFOTSNet)), enable)
+    """Switch a network whose type is exactly `FOTSNet` to `NativeMergeFOTSNet` (enable=False: back), and one that
+    `use_native_heads` / `use_native_recogniser` have switched to the class that has the merge as well (`_NETS` below).
+    Only the class of the network changes: no parameter is copied, no key of the state_dict moves.  A network of any
+    other type is left alone.  Returns whether the class was switched."""
+    return _sw.toggle_feature(net, _NETS, _NativeMerge, enable)
 
 
 # --------------------------------------------------------------------------- the stem's mirror and the blocks' tails, DESIGN 5.13
@@ -457,25 +435,14 @@ def use_native_blocks(net: nn.Module, enable: bool = True):
     (enable=False: back).  Only classes change: no parameter is copied, no key of the state_dict moves; the switches above
     compose with this one in any order.  Returns (mirror norms, plain blocks, separable blocks) switched: (2, 7, 10) for
     `FOTSNet()`."""
-    counts = [0, 0, 0]
-    for m in net.modules():
-        for k, (stock, native) in enumerate(_BLOCKS):
-            src, dst = (stock, native) if enable else (native, stock)
-            if type(m) is src:
-                m.__class__ = dst
-                counts[k] += 1
-                break
-    return tuple(counts)
+    return _sw.swap_classes(net, _BLOCKS, enable)
 
 
 # --------------------------------------------------------------------------- dense 3x3 convolutions, bf16 / fp16, DESIGN 5.15
-_CONV_DTYPES = (torch.bfloat16, torch.float16)
-
 
 def _dense_static_ok(m) -> bool:
     """What of `conv3x3_ok` depends on the module alone: an exact 3x3, padding 1, stride 1 or 2, groups 1, no bias."""
-    return (m.kernel_size == (3, 3) and m.padding == (1, 1) and m.dilation == (1, 1) and m.stride in ((1, 1), (2, 2))
-            and m.groups == 1 and m._parameters["bias"] is None and m.padding_mode == "zeros")
+    return _conv_static_ok(m, (3, 3), (1, 1)) and m.groups == 1
 
 
 def conv3x3_ok(m, x) -> bool:
@@ -483,16 +450,7 @@ def conv3x3_ok(m, x) -> bool:
     weight's (float32 keeps the stock Winograd kernels: DESIGN 5.15), a contiguous CUDA 4-D input of fewer than 2^31
     elements whose output stays below that too, no autocast, no gradient needed, and not one of the shape classes that
     measured slower (`_conv3x3_slower`)."""
-    w = m._parameters["weight"]
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype == w.dtype and x.dtype in _CONV_DTYPES
-            and x.is_contiguous() and _dense_static_ok(m) and x.size(1) == m.in_channels and w.device == x.device
-            and w.is_contiguous() and 0 < x.numel() < (1 << 31)):
-        return False
-    s = m.stride[0]
-    return (x.size(0) * m.out_channels * ((x.size(2) - 1) // s + 1) * ((x.size(3) - 1) // s + 1) < (1 << 31)
-            and not _conv3x3_slower(m, x)
-            and not torch.is_autocast_enabled()
-            and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)))
+    return _matrix_conv_ok(m, x, _dense_static_ok) and not _conv3x3_slower(m, x) and _inference(x, m._parameters["weight"])
 
 
 def _conv3x3_slower(m, x) -> bool:
@@ -511,9 +469,8 @@ def _conv3x3_slower(m, x) -> bool:
     Fewer than 16 input channels (the stem's 3>16) win at every measured size, 27/62 at one image and 186/375 at eight."""
     if m.in_channels < 16:
         return False
-    s = m.stride[0]
-    macs = x.size(0) * m.out_channels * ((x.size(2) - 1) // s + 1) * ((x.size(3) - 1) // s + 1) * 9 * m.in_channels
-    if s == 2:
+    macs = _conv_out_numel(m, x) * 9 * m.in_channels
+    if m.stride[0] == 2:
         return not (m.out_channels <= 32 and macs <= 2.5e9)
     return macs > (5.0e9 if x.dtype == torch.bfloat16 else 2.5e9)
 
@@ -563,40 +520,7 @@ def use_native_conv3x3(net: nn.Module, enable: bool = True, fuse_activation: boo
     own, so it and `use_native_instancenorm` leave each other's work alone in either order.  Whether a call runs the
     native kernel is decided per call by `conv3x3_ok` (float32 never does).  Returns (convolutions switched, activations
     absorbed)."""
-    convs = acts = 0
-    if not enable:
-        for m in net.modules():
-            if type(m) is DenseConv3x3:
-                m.__dict__.pop("fused_slope", None)
-                m.__class__ = nn.Conv2d
-                convs += 1
-            else:
-                for stock, applied in _CONV_APPLIED.items():
-                    if type(m) is applied:
-                        m.__class__ = stock
-                        acts += 1
-        return convs, acts
-    for m in net.modules():
-        if type(m) is nn.Conv2d and _dense_static_ok(m):
-            m.__class__ = DenseConv3x3
-            convs += 1
-    if fuse_activation:
-        uses = {}
-        for m in net.modules():
-            for child in m._modules.values():
-                if child is not None:
-                    uses[id(child)] = uses.get(id(child), 0) + 1
-        for seq in net.modules():
-            if not isinstance(seq, nn.Sequential):
-                continue
-            mods = list(seq._modules.values())
-            for conv, act in zip(mods, mods[1:]):
-                if (type(conv) is DenseConv3x3 and conv.fused_slope is None and type(act) in _CONV_APPLIED
-                        and uses[id(conv)] == 1 and uses[id(act)] == 1):
-                    conv.fused_slope = float(getattr(act, "negative_slope", 0.0))
-                    act.__class__ = _CONV_APPLIED[type(act)]
-                    acts += 1
-    return convs, acts
+    return _sw.swap_absorbing(net, nn.Conv2d, DenseConv3x3, _CONV_APPLIED, enable, fuse_activation, _dense_static_ok)
 
 
 # --------------------------------------------------------------------------- the recogniser, DESIGN 5.16
@@ -607,10 +531,7 @@ def act_pool_ok(x, slope: float = 0.01) -> bool:
     """True where `F.max_pool2d(F.leaky_relu(x, slope), (2, 1), stride=(2, 1))` (slope 1.0: the pool alone) may run the
     native kernel: pure, no GPU needed to ask.  A contiguous CUDA 4-D tensor of one of the three dtypes with at least two
     rows and fewer than 2^31 elements, no autocast, no gradient needed, and not a class of `_act_pool_slower`."""
-    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype in _DTYPES and x.is_contiguous()
-            and x.size(2) >= 2 and 0 < x.numel() < (1 << 31) and not _act_pool_slower(x, slope)
-            and not torch.is_autocast_enabled()
-            and not (torch.is_grad_enabled() and x.requires_grad))
+    return _tensor_ok(x) and x.size(2) >= 2 and not _act_pool_slower(x, slope) and _inference(x)
 
 
 def _act_pool_slower(x, slope: float = 0.01) -> bool:
@@ -632,15 +553,12 @@ def ocr_head_ok(net, x) -> bool:
     A contiguous CUDA (N, C, 1, T) tensor of one of the three dtypes, `conv11` a plain 1x1 convolution from C channels
     with parameters of that dtype on that device and at most 128 classes, fewer than 2^31 elements in and out, no
     autocast, no gradient needed, and not a class of `_ocr_head_slower`."""
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype in _DTYPES and x.is_contiguous()
-            and x.size(2) == 1 and 0 < x.numel() < (1 << 31)):
+    if not (_tensor_ok(x) and x.size(2) == 1):
         return False
     m = net._modules.get("conv11")
     return (type(m) is nn.Conv2d and 1 <= m.out_channels <= _OCR_HEAD_MAX_CLASSES
             and _pointwise_conv_ok(m, m.out_channels, x) and m._parameters["weight"].is_contiguous()
-            and x.size(0) * m.out_channels * x.size(3) < (1 << 31) and not _ocr_head_slower(m, x)
-            and not torch.is_autocast_enabled()
-            and not (torch.is_grad_enabled() and x.requires_grad))
+            and x.size(0) * m.out_channels * x.size(3) < (1 << 31) and not _ocr_head_slower(m, x) and _inference(x))
 
 
 def _ocr_head_slower(m, x) -> bool:
@@ -723,19 +641,23 @@ class NativeHeadsMergeRecogniserFOTSNet(_NativeRecogniser, NativeHeadsMergeFOTSN
 def use_native_recogniser(net: nn.Module, enable: bool = True) -> bool:
     """Switch a network whose type is exactly `FOTSNet`, `NativeHeadsFOTSNet`, `NativeMergeFOTSNet` or
     `NativeHeadsMergeFOTSNet` to the subclass of it with the native `forward_ocr` (enable=False: back to exactly that
-    type).  Only the class of the network changes: no parameter is copied, no key of the state_dict moves; it composes with
-    `use_native_heads`, `use_native_merge` and the module switches in any order.  A network of any other type is left
-    alone.  Returns whether the class was switched."""
-    return _switch_class(net, ((FOTSNet, NativeRecogniserFOTSNet), (NativeHeadsFOTSNet, NativeHeadsRecogniserFOTSNet),
-                               (NativeMergeFOTSNet, NativeMergeRecogniserFOTSNet),
-                               (NativeHeadsMergeFOTSNet, NativeHeadsMergeRecogniserFOTSNet)), enable)
+    type).  Only the class of the network changes: no parameter is copied, no key of the state_dict moves.  A network of
+    any other type is left alone.  Returns whether the class was switched."""
+    return _sw.toggle_feature(net, _NETS, _NativeRecogniser, enable)
+
+
+# The network classes by what they have: the heads from `NativeHeadsFOTSNet`, the merge from `_NativeMerge`, the recogniser
+# from `_NativeRecogniser`.  Read off the classes above: a class added there is in the table, a combination left out is not.
+# Each of the three switches toggles its own feature and nothing else, so they compose with each other, and with the
+# module switches, in any order (`fots_e2e._switching` has the rules for all thirteen).
+_FEATURES = (NativeHeadsFOTSNet, _NativeMerge, _NativeRecogniser)
+_NETS = _sw.feature_table([c for c in list(globals().values()) if isinstance(c, type) and issubclass(c, FOTSNet)], _FEATURES)
 
 
 # --------------------------------------------------------------------------- the 1x1 convolutions, DESIGN 5.17
 def _pointwise_static_ok(m) -> bool:
     """What of `conv1x1_ok` depends on the module alone: an exact 1x1, no padding, stride 1 or 2, groups 1, no bias."""
-    return (m.kernel_size == (1, 1) and m.padding == (0, 0) and m.dilation == (1, 1) and m.stride in ((1, 1), (2, 2))
-            and m.groups == 1 and m._parameters["bias"] is None and m.padding_mode == "zeros")
+    return _conv_static_ok(m, (1, 1), (0, 0)) and m.groups == 1
 
 
 def conv1x1_ok(m, x) -> bool:
@@ -743,16 +665,7 @@ def conv1x1_ok(m, x) -> bool:
     weight's (float32 keeps the stock path), a contiguous CUDA 4-D input of fewer than 2^31 elements whose output stays
     below that too, a contiguous weight on x's device, no autocast, no gradient needed, and not one of the shape classes
     that measured slower (`_conv1x1_slower`)."""
-    w = m._parameters["weight"]
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype == w.dtype and x.dtype in _CONV_DTYPES
-            and x.is_contiguous() and _pointwise_static_ok(m) and x.size(1) == m.in_channels and w.device == x.device
-            and w.is_contiguous() and 0 < x.numel() < (1 << 31)):
-        return False
-    s = m.stride[0]
-    return (x.size(0) * m.out_channels * ((x.size(2) - 1) // s + 1) * ((x.size(3) - 1) // s + 1) < (1 << 31)
-            and not _conv1x1_slower(m, x)
-            and not torch.is_autocast_enabled()
-            and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)))
+    return _matrix_conv_ok(m, x, _pointwise_static_ok) and not _conv1x1_slower(m, x) and _inference(x, m._parameters["weight"])
 
 
 def _conv1x1_slower(m, x) -> bool:
@@ -765,8 +678,7 @@ def _conv1x1_slower(m, x) -> bool:
     and 256>256 at 176x320 x 1 (3.7e9) 28.5/45.4 | 29.0/45.5; every shape of one image does, 9.2-16.9 against 44.8-60.2
     (the stock path is a chain of launches there, bound by what the host can issue); the line is drawn between the nearest
     measured rows on either side, 3.7e9 and 7.4e9."""
-    s = m.stride[0]
-    return x.size(0) * m.out_channels * ((x.size(2) - 1) // s + 1) * ((x.size(3) - 1) // s + 1) * m.in_channels > 5.5e9
+    return _conv_out_numel(m, x) * m.in_channels > 5.5e9
 
 
 class PointwiseConv1x1(nn.Conv2d):
@@ -835,22 +747,5 @@ def use_native_conv1x1(net: nn.Module, enable: bool = True):
     they leave these classes alone and compose with this one in any order.  Whether a call runs the native kernel is
     decided per call by `conv1x1_ok` / `shortcut_ok` (float32 never does).  Returns (convolutions switched, shortcuts
     switched)."""
-    convs = shortcuts = 0
-    if not enable:
-        for m in net.modules():
-            if type(m) is PointwiseConv1x1:
-                m.__class__ = nn.Conv2d
-                convs += 1
-            elif type(m) is NativeShortcut:
-                m.__class__ = nn.Sequential
-                shortcuts += 1
-        return convs, shortcuts
-    for m in net.modules():
-        if type(m) is nn.Conv2d and _pointwise_static_ok(m):
-            m.__class__ = PointwiseConv1x1
-            convs += 1
-    for m in net.modules():
-        if type(m) is nn.Sequential and _shortcut_pair(m) is not None:
-            m.__class__ = NativeShortcut
-            shortcuts += 1
-    return convs, shortcuts
+    return _sw.swap_classes(net, ((nn.Conv2d, PointwiseConv1x1), (nn.Sequential, NativeShortcut)), enable,
+                            lambda m: _pointwise_static_ok(m) if type(m) is nn.Conv2d else _shortcut_pair(m) is not None)

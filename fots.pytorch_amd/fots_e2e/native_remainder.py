@@ -20,25 +20,17 @@ closed list that the network tests read."""
 import torch
 import torch.nn as nn
 
+from . import _switching as _sw
 from . import native as _nat
 from .model import FOTSNet
 
-_REM = []
-
-
-def _rem():
-    """The ctypes binding of the two kernels, loaded on first use: asking a predicate needs neither the library nor a GPU."""
-    if not _REM:
-        from rroi_align._ext.rroi_align import remainder
-        _REM.append(remainder)
-    return _REM[0]
+_rem = _sw.lazy_module("rroi_align._ext.rroi_align.remainder")   # the binding of the two kernels, loaded on first use
 
 
 # --------------------------------------------------------------------------- the (2,3) convolution, bf16 / fp16, DESIGN 5.19
 def _conv2x3_static_ok(m) -> bool:
     """What of `conv2x3_ok` depends on the module alone: an exact (2,3), padding (0,1), stride 1, groups 1, no bias."""
-    return (m.kernel_size == (2, 3) and m.padding == (0, 1) and m.dilation == (1, 1) and m.stride == (1, 1)
-            and m.groups == 1 and m._parameters["bias"] is None and m.padding_mode == "zeros")
+    return _nat._conv_static_ok(m, (2, 3), (0, 1), ((1, 1),)) and m.groups == 1
 
 
 def conv2x3_ok(m, x) -> bool:
@@ -47,14 +39,9 @@ def conv2x3_ok(m, x) -> bool:
     of at least two rows and fewer than 2^31 elements whose output stays below that too, a contiguous weight on x's
     device, no autocast, no gradient needed, and not one of the shape classes that measured slower (`_conv2x3_slower`)."""
     w = m._parameters["weight"]
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype == w.dtype and x.dtype in _nat._CONV_DTYPES
-            and x.is_contiguous() and _conv2x3_static_ok(m) and x.size(1) == m.in_channels and w.device == x.device
-            and w.is_contiguous() and x.size(2) >= 2 and 0 < x.numel() < (1 << 31)):
-        return False
-    return (x.size(0) * m.out_channels * (x.size(2) - 1) * x.size(3) < (1 << 31)
-            and not _conv2x3_slower(m, x)
-            and not torch.is_autocast_enabled()
-            and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)))
+    return (_nat._tensor_ok(x, _nat._CONV_DTYPES) and _conv2x3_static_ok(m) and _nat._conv_operands_ok(m, x)
+            and w.is_contiguous() and x.size(2) >= 2 and x.size(0) * m.out_channels * (x.size(2) - 1) * x.size(3) < (1 << 31)
+            and not _conv2x3_slower(m, x) and _nat._inference(x, w))
 
 
 def _conv2x3_slower(m, x) -> bool:
@@ -86,13 +73,7 @@ def use_native_conv2x3(net: nn.Module, enable: bool = True) -> int:
     it composes with them in any order.  `FOTSNet.forward_ocr` calls `self.conv10_s(x)`, stock or native recogniser, and so
     picks the class up.  Whether a call runs the native kernel is decided per call by `conv2x3_ok` (float32 never does).
     Returns the number of modules switched (1 for `FOTSNet()`)."""
-    src, dst = (nn.Conv2d, DenseConv2x3) if enable else (DenseConv2x3, nn.Conv2d)
-    n = 0
-    for m in net.modules():
-        if type(m) is src and (not enable or _conv2x3_static_ok(m)):
-            m.__class__ = dst
-            n += 1
-    return n
+    return _sw.swap_classes(net, ((nn.Conv2d, DenseConv2x3),), enable, _conv2x3_static_ok)[0]
 
 
 # --------------------------------------------------------------------------- resize + depthwise 3x3, DESIGN 5.20
@@ -122,6 +103,7 @@ def up_depthwise_ok(seq, t, like) -> bool:
     class of `_up_depthwise_slower`."""
     mods = seq._modules
     dw = next(iter(mods.values())) if mods else None
+    # (the clauses of `native._tensor_ok` and `native._inference` written out: through the helpers this one measured slower)
     if not (isinstance(dw, nn.Conv2d) and isinstance(t, torch.Tensor) and isinstance(like, torch.Tensor) and t.is_cuda
             and t.dim() == 4 and like.dim() == 4 and t.dtype in _nat._DTYPES and t.is_contiguous()):
         return False
@@ -163,12 +145,4 @@ def use_native_upconv(net: nn.Module, enable: bool = True) -> int:
     other switches in any order.  Without `use_native_merge` this switch has NO effect on what runs: only the native
     merge (`native._NativeMerge._merge`) hands the block the map before its resize; the stock `FOTSNet._merge` resizes
     first and calls the block as the Sequential it is.  Returns the number of blocks switched (2 for `FOTSNet()`)."""
-    n = 0
-    for m in net.modules():
-        if enable and type(m) is nn.Sequential and _smooth_pair(m) is not None:
-            m.__class__ = UpSmooth
-            n += 1
-        elif not enable and type(m) is UpSmooth:
-            m.__class__ = nn.Sequential
-            n += 1
-    return n
+    return _sw.swap_classes(net, ((nn.Sequential, UpSmooth),), enable, lambda m: _smooth_pair(m) is not None)[0]

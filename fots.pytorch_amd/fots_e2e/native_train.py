@@ -27,28 +27,33 @@ and raises under `torch.use_deterministic_algorithms(True)` -- has native gradie
 `_merge`, in training mode, runs the three merges and the two stand-alone resizes through `rroi_align.merge`'s autograd
 functions where a gradient is needed and `trainable_merge_ok` holds.
 
+The order, for all three: a trainable switch extends the class its native switch makes, so it goes on after that switch
+and comes off before it.  A native switch undone while its trainable one is still on finds no class of its own, changes
+nothing and returns zero counts; the network computes what it did (`fots_e2e._switching`).
+
 It lives in a module of its own for the reason `native_remainder` does: the `_*_slower` hooks of `fots_e2e.native` are a
 closed list that the network tests read."""
 import torch
 import torch.nn as nn
 
+from . import _switching as _sw
 from . import native as _nat
 
-_NORM = []
+# The autograd functions, each module loaded on first use: asking a predicate needs neither the library nor a GPU.
+_norm = _sw.lazy_module("rroi_align.norm")
+_conv = _sw.lazy_module("rroi_align.conv")
+_merge_fn = _sw.lazy_module("rroi_align.merge")
 
 
-def _norm():
-    """`rroi_align.norm`, loaded on first use: asking the predicate needs neither the library nor a GPU."""
-    if not _NORM:
-        from rroi_align import norm
-        _NORM.append(norm)
-    return _NORM[0]
+def _any_needs_grad(tensors, params) -> bool:
+    """Whether autograd wants a gradient through one of `tensors` or into one of `params` (None: an absent parameter)."""
+    return torch.is_grad_enabled() and (any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+                                        or any(p is not None and p.requires_grad for p in params))
 
 
 def _needs_grad(m, x) -> bool:
-    if not (isinstance(x, torch.Tensor) and torch.is_grad_enabled()):
-        return False
-    return x.requires_grad or any(p is not None and p.requires_grad for p in (m._parameters.get("weight"), m._parameters.get("bias")))
+    """Whether `m(x)` needs a gradient: through the tensor x, or into a parameter of m's own."""
+    return isinstance(x, torch.Tensor) and _any_needs_grad((x,), m._parameters.values())
 
 
 def trainable_norm_ok(m, x) -> bool:
@@ -90,31 +95,14 @@ class TrainableInstanceNorm2d(_nat.NativeInstanceNorm2d):
 
 
 def use_trainable_instancenorm(net: nn.Module, enable: bool = True) -> int:
-    """Switch every `NativeInstanceNorm2d` of `net` to `TrainableInstanceNorm2d` (enable=False: back), so call it after
-    `native.use_native_instancenorm` and undo it before undoing that.  Only the class of a module changes: no parameter
-    is copied, no key of the state_dict moves, a `fused_slope` stays.  Returns the number of modules switched (52 for
+    """Switch every `NativeInstanceNorm2d` of `net` to `TrainableInstanceNorm2d` (enable=False: back): on after
+    `native.use_native_instancenorm`, off before it (the module docstring).  Only the class of a module changes: no
+    parameter is copied, no key of the state_dict moves, a `fused_slope` stays.  Returns the number of modules switched (52 for
     `FOTSNet()`)."""
-    src, dst = (_nat.NativeInstanceNorm2d, TrainableInstanceNorm2d) if enable else (TrainableInstanceNorm2d, _nat.NativeInstanceNorm2d)
-    n = 0
-    for m in net.modules():
-        if type(m) is src:
-            m.__class__ = dst
-            n += 1
-    return n
+    return _sw.swap_classes(net, ((_nat.NativeInstanceNorm2d, TrainableInstanceNorm2d),), enable)[0]
 
 
 # --------------------------------------------------------------------------- depthwise 3x3 convolution, DESIGN 5.25
-_CONV = []
-
-
-def _conv():
-    """`rroi_align.conv`, loaded on first use, as `_norm`."""
-    if not _CONV:
-        from rroi_align import conv
-        _CONV.append(conv)
-    return _CONV[0]
-
-
 def trainable_depthwise_ok(m, x) -> bool:
     """True where `m(x)` may run the native forward and backward when a gradient is needed: `native.native_ok`'s conditions
     other than its gradient clause (asked with gradients off, so that there is one copy of them), and not a shape class
@@ -146,37 +134,20 @@ class TrainableDepthwiseConv3x3(_nat.DepthwiseConv3x3):
     gradient, native deterministic weight gradient."""
 
     def forward(self, x):
-        w = self._parameters["weight"]
-        if (isinstance(x, torch.Tensor) and torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)
-                and trainable_depthwise_ok(self, x)):
-            return _conv()._Depthwise3x3.apply(x, w, self.stride[0])
+        if _needs_grad(self, x) and trainable_depthwise_ok(self, x):
+            return _conv()._Depthwise3x3.apply(x, self._parameters["weight"], self.stride[0])
         return super().forward(x)
 
 
 def use_trainable_depthwise(net: nn.Module, enable: bool = True) -> int:
-    """Switch every `DepthwiseConv3x3` of `net` to `TrainableDepthwiseConv3x3` (enable=False: back), so call it after
-    `native.use_native_depthwise` and undo it before undoing that.  Only the class of a module changes: no parameter is
-    copied, no key of the state_dict moves.  Returns the number of modules switched (22 for `FOTSNet()`)."""
-    src, dst = (_nat.DepthwiseConv3x3, TrainableDepthwiseConv3x3) if enable else (TrainableDepthwiseConv3x3, _nat.DepthwiseConv3x3)
-    n = 0
-    for m in net.modules():
-        if type(m) is src:
-            m.__class__ = dst
-            n += 1
-    return n
+    """Switch every `DepthwiseConv3x3` of `net` to `TrainableDepthwiseConv3x3` (enable=False: back): on after
+    `native.use_native_depthwise`, off before it (the module docstring).  Only the class of a module changes: no
+    parameter is copied, no key of the state_dict moves.  Returns the number of modules switched (22 for `FOTSNet()`)."""
+    return _sw.swap_classes(net, ((_nat.DepthwiseConv3x3, TrainableDepthwiseConv3x3),), enable)[0]
 
 
 # --------------------------------------------------------------------------- the feature merge, DESIGN 5.26
-_MERGE = []
 _MAX_FOOTPRINT = 4096     # kRsMaxFootprint of csrc/rroi_merge_backward_kernels.h
-
-
-def _merge_fn():
-    """`rroi_align.merge`, loaded on first use, as `_norm`."""
-    if not _MERGE:
-        from rroi_align import merge
-        _MERGE.append(merge)
-    return _MERGE[0]
 
 
 def _footprint_bound(n_in: int, n_out: int) -> int:
@@ -248,10 +219,8 @@ class _TrainableMerge:
         return A + f if g is None else A + f * self._up(g, f)
 
     def _merge(self, f1, f2, f3, f4):
-        if not (self.training and torch.is_grad_enabled()
-                and (any(isinstance(t, torch.Tensor) and t.requires_grad for t in (f1, f2, f3, f4))
-                     or (self.attention and any(p.requires_grad for p in self.conv_attenton.parameters()))
-                     or any(p.requires_grad for m in (self.upconv1, self.upconv2) for p in m.parameters()))):
+        own = (self.conv_attenton, self.upconv1, self.upconv2) if self.attention else (self.upconv1, self.upconv2)
+        if not (self.training and _any_needs_grad((f1, f2, f3, f4), (p for m in own for p in m.parameters()))):
             return super()._merge(f1, f2, f3, f4)
         t = self._train_merge_one(f4, f3, f4)
         m2 = self._train_merge_one(self.upconv1(self._train_resize(t, f2)), f2, t)
@@ -277,11 +246,14 @@ class TrainableHeadsMergeRecogniserFOTSNet(_TrainableMerge, _nat.NativeHeadsMerg
 
 def use_trainable_merge(net: nn.Module, enable: bool = True) -> bool:
     """Switch a network whose type is exactly one of the four `*Merge*FOTSNet` classes of `fots_e2e.native` to its trainable
-    subclass (enable=False: back), so call it after `native.use_native_merge` -- and after `use_native_heads` /
-    `use_native_recogniser`, which look for the exact types they know -- and undo it before undoing those.  Only the class
+    subclass (enable=False: back): on after `native.use_native_merge` -- and after `use_native_heads` /
+    `use_native_recogniser`, which look for the exact types they know -- and off before them.  Only the class
     of the network changes: no parameter is copied, no key of the state_dict moves.  A network of any other type is left
     alone.  Returns whether the class was switched."""
-    return _nat._switch_class(net, ((_nat.NativeMergeFOTSNet, TrainableMergeFOTSNet),
-                                    (_nat.NativeHeadsMergeFOTSNet, TrainableHeadsMergeFOTSNet),
-                                    (_nat.NativeMergeRecogniserFOTSNet, TrainableMergeRecogniserFOTSNet),
-                                    (_nat.NativeHeadsMergeRecogniserFOTSNet, TrainableHeadsMergeRecogniserFOTSNet)), enable)
+    return _sw.toggle_feature(net, _NETS, _TrainableMerge, enable)
+
+
+# Every trainable class (read off the classes above) and the native class it extends, its second base, by what they have.
+_TRAINABLE = [c for c in list(globals().values())
+              if isinstance(c, type) and issubclass(c, _TrainableMerge) and c is not _TrainableMerge]
+_NETS = _sw.feature_table(_TRAINABLE + [c.__bases__[1] for c in _TRAINABLE], _nat._FEATURES + (_TrainableMerge,))
