@@ -41,7 +41,8 @@
 // rroi_instancenorm_backward_kernels.h (+ rroi_instancenorm_backward_host.h: the InstanceNorm's training forward and its
 // backward), rroi_depthwise_backward_kernels.h (+ rroi_depthwise_backward_host.h: the depthwise 3x3
 // convolution's input and weight gradients), rroi_merge_backward_kernels.h (+ rroi_merge_backward_host.h: the
-// gated merge's backward, the stand-alone resize and its backward).
+// gated merge's backward, the stand-alone resize and its backward), rroi_heads_backward_kernels.h
+// (+ rroi_heads_backward_host.h: the heads' and the gate's training forward and their backward).
 // Host side: rroi_host_plan.h (tuning table,
 // Shape, limits, workspace carvers, the dispatch: what a call launches, down to every grid), rroi_host_scratch.h (the
 // launchers' scratch), rroi_host_launch.h (the launches: one function per kernel template, run from the plan's fields).
@@ -86,6 +87,7 @@ namespace {
 #include "rroi_instancenorm_backward_kernels.h"
 #include "rroi_depthwise_backward_kernels.h"
 #include "rroi_merge_backward_kernels.h"
+#include "rroi_heads_backward_kernels.h"
 
 #include "rroi_host_plan.h"
 #include "rroi_host_scratch.h"
@@ -105,6 +107,7 @@ namespace {
 #include "rroi_instancenorm_backward_host.h"
 #include "rroi_depthwise_backward_host.h"
 #include "rroi_merge_backward_host.h"
+#include "rroi_heads_backward_host.h"
 
 }  // namespace
 
@@ -842,6 +845,125 @@ int rroi_gate_forward_hip(int dtype, const void* x, const void* w, const void* b
                                                      static_cast<const T*>(nullptr), static_cast<T*>(y), static_cast<T*>(nullptr),
                                                      static_cast<T*>(nullptr), (unsigned)channels, 1.0, stream);
     });
+}
+
+// Their training forward and backward (header section 7b): the forward with z as one more output, and a
+// backward of one launch for dx, two and a workspace where a parameter gradient is wanted.
+int rroi_heads_forward_train_hip(int dtype, const void* x, const void* w_score, const void* b_score, const void* w_rbox,
+                                 const void* b_rbox, const void* w_angle, const void* b_angle, void* score, void* rbox,
+                                 void* angle, void* z, int batch_size, int channels, int height, int width, double rbox_scale,
+                                 void* stream_)
+{
+    const HeadsPlan P = plan_heads(dtype, 7, batch_size, channels, height, width, num_cus());
+    if (!P.status) return 0;
+    if (!x || !w_score || !w_rbox || !w_angle || !score || !rbox || !angle || !z) return 0;
+    if (!std::isfinite(rbox_scale)) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return launch_pointwise_train<T, 7, kPwEpiHeads>(
+            P, static_cast<const T*>(x), static_cast<const T*>(w_score), static_cast<const T*>(b_score),
+            static_cast<const T*>(w_rbox), static_cast<const T*>(b_rbox), static_cast<const T*>(w_angle),
+            static_cast<const T*>(b_angle), static_cast<T*>(score), static_cast<T*>(rbox), static_cast<T*>(angle),
+            static_cast<double*>(z), (unsigned)channels, rbox_scale, stream);
+    });
+}
+
+int rroi_gate_forward_train_hip(int dtype, const void* x, const void* w, const void* b, void* y, void* z, int batch_size,
+                                int channels, int height, int width, void* stream_)
+{
+    const HeadsPlan P = plan_heads(dtype, 1, batch_size, channels, height, width, num_cus());
+    if (!P.status) return 0;
+    if (!x || !w || !y || !z) return 0;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        const T* none = nullptr;
+        return launch_pointwise_train<T, 1, kPwEpiSigmoid>(P, static_cast<const T*>(x), static_cast<const T*>(w),
+                                                           static_cast<const T*>(b), none, none, none, none, static_cast<T*>(y),
+                                                           static_cast<T*>(nullptr), static_cast<T*>(nullptr),
+                                                           static_cast<double*>(z), (unsigned)channels, 1.0, stream);
+    });
+}
+
+int rroi_heads_backward_plan(int dtype, int outputs, int batch_size, int channels, int height, int width,
+                             rroi_heads_backward_plan_info* plan)
+{
+    const HeadsBwdPlan P = plan_heads_backward(dtype, outputs, batch_size, channels, height, width, num_cus());
+    if (!P.status || !plan) return 0;
+    // launches: of a call that wants a parameter gradient (dx alone is one)
+    *plan = rroi_heads_backward_plan_info{P.V, (int)P.rows, (int)P.rows, (int)P.tpw, kHbThreads, (int)P.lds_bytes, 2, 0,
+                                          (long long)P.tpw * 64 * P.V, (long long)P.ws_bytes};
+    return 1;
+}
+
+size_t rroi_heads_backward_workspace_bytes(int outputs, int batch_size, int channels, int height, int width)
+{
+    return plan_heads_backward(RROI_DTYPE_FP32, outputs, batch_size, channels, height, width, num_cus()).ws_bytes;   // no dtype in the rule
+}
+
+// an argument's memory; NULL overlaps nothing
+struct HbSpan { const void* p; size_t bytes; };
+
+static int heads_backward_impl(int dtype, int outputs, const void* g0, const void* g1, const void* g2, const void* x,
+                               const void* z, const void* w0, const void* w1, const void* w2, void* dx, void* const (&dwb)[6],
+                               int batch_size, int channels, int height, int width, double rbox_scale, void* workspace,
+                               size_t workspace_bytes, void* stream_)
+{
+    const HeadsBwdPlan P = plan_heads_backward(dtype, outputs, batch_size, channels, height, width, num_cus());
+    if (!P.status || !std::isfinite(rbox_scale)) return 0;
+    const bool heads = outputs == 7;
+    if (!x || !z || (!g0 && !g1 && !g2)) return 0;
+    bool params = false;
+    for (const void* p : dwb) params = params || p;
+    if (!dx && !params) return 0;
+    if (dx && (!w0 || (heads && (!w1 || !w2)))) return 0;
+    if (params && (!workspace_ok(workspace) || workspace_bytes < P.ws_bytes)) return 0;
+    const size_t esize = dtype_bytes(dtype), px = (size_t)batch_size * P.hw, C = (size_t)channels;
+    const HbSpan ins[] = {{g0, px * esize}, {g1, 4 * px * esize}, {g2, 2 * px * esize}, {x, px * C * esize},
+                          {z, px * outputs * sizeof(double)}, {w0, C * esize}, {w1, 4 * C * esize}, {w2, 2 * C * esize}};
+    const HbSpan outs[] = {{dx, px * C * esize}, {dwb[0], C * esize}, {dwb[1], esize}, {dwb[2], 4 * C * esize},
+                           {dwb[3], 4 * esize}, {dwb[4], 2 * C * esize}, {dwb[5], 2 * esize},
+                           {params ? workspace : nullptr, P.ws_bytes}};
+    for (size_t a = 0; a < sizeof(outs) / sizeof(outs[0]); ++a) {
+        for (const HbSpan& in : ins)
+            if (bytes_overlap(outs[a].p, outs[a].bytes, in.p, in.bytes)) return 0;
+        for (size_t b = a + 1; b < sizeof(outs) / sizeof(outs[0]); ++b)
+            if (bytes_overlap(outs[a].p, outs[a].bytes, outs[b].p, outs[b].bytes)) return 0;
+    }
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return with_dtype(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        const auto in = [](const void* p) { return static_cast<const T*>(p); };
+        const auto out = [](void* p) { return static_cast<T*>(p); };
+        if (heads)
+            return launch_heads_backward<T, 7>(P, in(g0), in(g1), in(g2), in(x), static_cast<const double*>(z), in(w0), in(w1),
+                                               in(w2), out(dx), out(dwb[0]), out(dwb[1]), out(dwb[2]), out(dwb[3]), out(dwb[4]),
+                                               out(dwb[5]), (unsigned)channels, rbox_scale, workspace, stream);
+        return launch_heads_backward<T, 1>(P, in(g0), in(nullptr), in(nullptr), in(x), static_cast<const double*>(z), in(w0),
+                                           in(nullptr), in(nullptr), out(dx), out(dwb[0]), out(dwb[1]), out(nullptr),
+                                           out(nullptr), out(nullptr), out(nullptr), (unsigned)channels, 1.0, workspace, stream);
+    });
+}
+
+int rroi_heads_backward_hip(int dtype, const void* dscore, const void* drbox, const void* dangle, const void* x, const void* z,
+                            const void* w_score, const void* w_rbox, const void* w_angle, void* dx, void* dw_score,
+                            void* db_score, void* dw_rbox, void* db_rbox, void* dw_angle, void* db_angle, int batch_size,
+                            int channels, int height, int width, double rbox_scale, void* workspace, size_t workspace_bytes,
+                            void* stream)
+{
+    void* const dwb[6] = {dw_score, db_score, dw_rbox, db_rbox, dw_angle, db_angle};
+    return heads_backward_impl(dtype, 7, dscore, drbox, dangle, x, z, w_score, w_rbox, w_angle, dx, dwb, batch_size, channels,
+                               height, width, rbox_scale, workspace, workspace_bytes, stream);
+}
+
+int rroi_gate_backward_hip(int dtype, const void* dy, const void* x, const void* z, const void* w, void* dx, void* dw, void* db,
+                           int batch_size, int channels, int height, int width, void* workspace, size_t workspace_bytes,
+                           void* stream)
+{
+    void* const dwb[6] = {dw, db, nullptr, nullptr, nullptr, nullptr};
+    return heads_backward_impl(dtype, 1, dy, nullptr, nullptr, x, z, w, nullptr, nullptr, dx, dwb, batch_size, channels, height,
+                               width, 1.0, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------

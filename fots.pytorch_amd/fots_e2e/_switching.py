@@ -1,11 +1,12 @@
-"""fots_e2e._switching -- what the switches of `native`, `native_remainder` and `native_train` share: the lazy loader of a
-library module, the class swap over a network's modules, the absorption of an activation into the module in front of it,
+"""fots_e2e._switching -- what the switches of `native`, `native_remainder`, `native_train` and `native_train_heads`
+share: the lazy loader of a library module, the class swap over a network's modules, the absorption of an activation into the module in front of it,
 and the table that maps a set of features to the network class that has them.
 
 How the switches compose and undo, said once.  Every switch changes classes only and tests exact types, so the switches
 leave each other's classes alone and compose in any order, with two rules: a `use_trainable_*` switch goes on after the
 `use_native_*` switch whose class it extends and comes off before it, and `use_trainable_merge` goes on after, and comes
-off before, `use_native_heads` / `use_native_recogniser` as well.  A switch undone out of that order finds no class of its
+off before, `use_native_heads` / `use_native_recogniser` as well; `native_train_heads.use_trainable_heads` goes on after
+all of them and comes off first.  A switch undone out of that order finds no class of its
 own, changes nothing and says so in what it returns; the network computes what it did before the call."""
 import importlib
 

@@ -202,7 +202,7 @@ def _merge_backward_slower(a, f, gate, resize_only) -> bool:
 
 class _TrainableMerge:
     """Mixin in front of a `*Merge*FOTSNet`: in training mode, where a gradient is needed, `_merge` runs the three merges
-    through `rroi_align.merge.gated_merge` -- the gate at its source's size from `torch.sigmoid(self.conv_attenton(t))`
+    through `rroi_align.merge.gated_merge` -- the gate at its source's size from `_train_gate`: `torch.sigmoid(self.conv_attenton(t))`
     under stock autograd -- and the two resizes in front of `upconv1` / `upconv2` through `bilinear_resize`, each where
     `trainable_merge_ok` holds and as `FOTSNet._merge`'s expression where it does not.  Everywhere else it is its parent."""
 
@@ -211,8 +211,12 @@ class _TrainableMerge:
             return _merge_fn()._BilinearResize.apply(t, like.size(2), like.size(3))
         return self._up(t, like)
 
+    def _train_gate(self, t):
+        """The gate at its source's size, under stock autograd (`native_train_heads` overrides it)."""
+        return torch.sigmoid(self.conv_attenton(t))
+
     def _train_merge_one(self, a, f, t):
-        g = torch.sigmoid(self.conv_attenton(t)) if self.attention else None
+        g = self._train_gate(t) if self.attention else None
         if trainable_merge_ok(a, f, g):
             return _merge_fn()._GatedMerge.apply(a, f, g)
         A = a if a.shape[2:] == f.shape[2:] else self._up(a, f)

@@ -44,7 +44,9 @@ from .instancenorm import (INORM_PLANE, INORM_SPLIT, InstanceNormPlan, _InormPla
                            instance_norm_backward_workspace_bytes, instance_norm_fused, instance_norm_plan,
                            instance_norm_train, instance_norm_workspace_bytes, run_instance_norm_backward,
                            run_instance_norm_train)
-from .heads import HeadsPlan, _gate_run, _heads_run, _HeadsPlan, _require_pointwise, gate, heads, heads_plan  # noqa: F401
+from .heads import (HeadsBackwardPlan, HeadsPlan, _gate_run, _heads_run, _HeadsBwdPlan, _HeadsPlan, _require_pointwise,  # noqa: F401
+                    gate, gate_backward, gate_train, heads, heads_backward, heads_backward_plan, heads_backward_workspace_bytes,
+                    heads_plan, heads_train, run_gate_backward, run_gate_train, run_heads_backward, run_heads_train)
 from .merge import (MergeBackwardPlan, MergePlan, ResizeBackwardPlan, _gated_merge_run, _MergeBwdPlan, _MergePlan,  # noqa: F401
                     _ResizeBwdPlan, gated_merge, gated_merge_backward, merge_backward_plan, merge_backward_workspace_bytes,
                     merge_plan, resize_backward_plan, resize_bilinear, resize_bilinear_backward, resize_footprint,
@@ -85,4 +87,6 @@ EXPORTS = (
     "rroi_depthwise3x3_backward_hip", "rroi_depthwise3x3_backward_workspace_bytes", "rroi_depthwise3x3_backward_plan",
     "rroi_resize_forward_hip", "rroi_resize_backward_hip", "rroi_resize_footprint", "rroi_resize_backward_plan",
     "rroi_merge_backward_hip", "rroi_merge_backward_workspace_bytes", "rroi_merge_backward_plan",   # bound in merge.py
+    "rroi_heads_forward_train_hip", "rroi_gate_forward_train_hip", "rroi_heads_backward_hip", "rroi_gate_backward_hip",
+    "rroi_heads_backward_workspace_bytes", "rroi_heads_backward_plan",   # bound in heads.py
 )

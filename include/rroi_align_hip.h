@@ -765,6 +765,78 @@ int rroi_gate_forward_hip(int dtype, const void* x, const void* w, const void* b
 int rroi_heads_plan(int dtype, int outputs, int batch_size, int channels, int height, int width, rroi_heads_plan_info* plan);
 
 /* ------------------------------------------------------------------------- *
+ * 7b. The heads and the gate where a gradient is needed: a training forward that leaves what the backward
+ *    needs, and a deterministic backward without atomics.  Opt-in from Python (rroi_align.heads.detection_heads /
+ *    attention_gate, fots_e2e.native_train_heads.use_trainable_heads).  Tensors as in section 7, and
+ *
+ *      z        (N, 7 | 1, H, W)  DOUBLE, contiguous: the pre-activation sums z_o of section 7
+ *      dscore (N, 1, H, W)  drbox (N, 4, H, W)  dangle (N, 2, H, W)  (gate: dy (N, 1, H, W))   element type `dtype`
+ *      dx (N, C, H, W)   dw_* (k, C)   db_* (k)                                                element type `dtype`
+ *
+ *    rroi_heads_forward_train_hip / rroi_gate_forward_train_hip: the call of section 7 with one more output.  z holds
+ *      z_o = b_o + p_0 + ... + p_{S-1} exactly as section 7 forms it, with the same plan; the other outputs have the bits
+ *      of rroi_heads_forward_hip / rroi_gate_forward_hip.  One launch.  Refuses what section 7 refuses, and a NULL z.
+ *
+ *    rroi_heads_backward_hip / rroi_gate_backward_hip: each of dscore, drbox, dangle may be NULL, which means zero, not
+ *      all of them (gate: dy is needed); each of dx, dw_*, db_* may be NULL and is then not computed, not all of them.
+ *      Per pixel, in double, every operation rounded once except the fused multiply-adds named below:
+ *        s_o = 1 / (1 + exp(-z_o));  g_0 = dscore;  g_{1+j} = rbox_scale * drbox_j
+ *        a_i = 2 s_{5+i} - 1,  r = sqrt(a_0 a_0 + a_1 a_1),  u_i = a_i / r,  p = u_0 dangle_0 + u_1 dangle_1
+ *        g_{5+i} = 2 (dangle_i - u_i p) / r;   dz_o = g_o * (s_o * (1 - s_o))        (gate: g_0 = dy, one output)
+ *        dx_c = fma(w[6][c], dz_6, ... fma(w[0][c], dz_0, +0.0));   out = (T)(float)dx_c, as section 7 rounds
+ *      r = 0 gives NaN in that pixel's dx column, as the stock chain's backward does; a non-finite value in a pixel
+ *      affects that pixel's dx column and the parameter gradients alone; no channel and no output is skipped.
+ *        dw[o][c] = sum over (n, pixel) of dz_o x[c],   db[o] = sum over (n, pixel) of dz_o
+ *      in double, each term of dw entering by one fused multiply-add, in an order the plan alone fixes and without
+ *      atomics: a lane adds its `vector_elems` pixels, the 64 lanes of a wave are added pairwise (lane l with l ^ 32,
+ *      then ^ 16, ... ^ 1), a workgroup adds its `tiles_per_workgroup` tiles in tile order and leaves ONE partial row of
+ *      k (C + 1) doubles -- dw [o][c], then db [o] -- in the workspace; a second launch adds the rows, four quarters of
+ *      the rows each in row order and then the quarters in order, and rounds once, out = (T)(float)sum.  So a backward is
+ *      two launches, and one where no parameter gradient is wanted.  The plan depends on (dtype, outputs, N, C, H, W, CU
+ *      count) alone -- 256 CUs where there is no GPU -- so identical calls give identical bits at any addresses.
+ *      The workspace: rroi_heads_backward_workspace_bytes(...) bytes at a 256-byte-aligned address where a dw or db is
+ *      wanted; the partial rows never exceed four per CU, whatever N * H * W is.  Its contents before and after the call
+ *      mean nothing.  Where no dw or db is wanted it is not needed: NULL / 0 is accepted.
+ *
+ *    Returns 1 / 0 / -hipError.  0, before any launch: everything section 7 refuses, k (C + 1) >= 2^31, a NULL x or z, a
+ *    NULL weight while dx is wanted, no output gradient given, no output wanted, a workspace that is NULL, misaligned or
+ *    too small while a dw or db is wanted, an output overlapping an input, another output or the workspace.  The calls
+ *    only enqueue on `stream` and allocate nothing: they can be captured into a HIP graph.
+ *    Arrived after 0.10.0 under the same version string: detect them by symbol.
+ * ------------------------------------------------------------------------- */
+typedef struct rroi_heads_backward_plan_info {
+    int vector_elems;          /* V: consecutive pixels per lane (2 or 1) */
+    int grid_x;                /* workgroups of the main launch */
+    int partial_rows;          /* rows of k (C + 1) doubles in the workspace: one per workgroup */
+    int tiles_per_workgroup;   /* tiles of 64 * V pixels a workgroup walks */
+    int block;                 /* threads per workgroup: 256 */
+    int lds_bytes;             /* of a main launch that leaves partial rows */
+    int launches;              /* of a call that wants a dw or db: 2 (dx alone: 1) */
+    int reserved;
+    long long pixels_per_workgroup;   /* tiles_per_workgroup * 64 * V */
+    long long workspace_bytes;        /* partial_rows * k * (C + 1) * 8 */
+} rroi_heads_backward_plan_info;
+int rroi_heads_forward_train_hip(int dtype, const void* x, const void* w_score, const void* b_score, const void* w_rbox,
+                                 const void* b_rbox, const void* w_angle, const void* b_angle, void* score, void* rbox,
+                                 void* angle, void* z, int batch_size, int channels, int height, int width, double rbox_scale,
+                                 void* stream);
+int rroi_gate_forward_train_hip(int dtype, const void* x, const void* w, const void* b, void* y, void* z, int batch_size,
+                                int channels, int height, int width, void* stream);
+int rroi_heads_backward_hip(int dtype, const void* dscore, const void* drbox, const void* dangle, const void* x, const void* z,
+                            const void* w_score, const void* w_rbox, const void* w_angle, void* dx, void* dw_score,
+                            void* db_score, void* dw_rbox, void* db_rbox, void* dw_angle, void* db_angle, int batch_size,
+                            int channels, int height, int width, double rbox_scale, void* workspace, size_t workspace_bytes,
+                            void* stream);
+int rroi_gate_backward_hip(int dtype, const void* dy, const void* x, const void* z, const void* w, void* dx, void* dw, void* db,
+                           int batch_size, int channels, int height, int width, void* workspace, size_t workspace_bytes,
+                           void* stream);
+/* host only; outputs: 7 (heads) or 1 (gate); 0 for arguments the call would refuse */
+size_t rroi_heads_backward_workspace_bytes(int outputs, int batch_size, int channels, int height, int width);
+/* host only, no launch; 1, or 0 for arguments the call would refuse */
+int rroi_heads_backward_plan(int dtype, int outputs, int batch_size, int channels, int height, int width,
+                             rroi_heads_backward_plan_info* plan);
+
+/* ------------------------------------------------------------------------- *
  * 8. The gated merge of the network's feature merge: y = A + f * G in ONE launch, where A is `a` resized
  *    to f's size and G the one-channel `gate` resized likewise -- `up(a) + f * up(gate)` of tools/models.py:412-434.
  *    Forward only; opt-in from Python (fots_e2e.native.use_native_merge).
